@@ -21,8 +21,12 @@ The headline batch is drawn by tests/problems.py:make_lqr_batch_spd -- the refer
 make_lqr (tfmpc/envs/__init__.py:9-18) vectorised: F, f, c ~ N(0,1), C by make_spd_matrix's
 formula (eigenvalues ~1e-3 .. n+m).
 
-Prints ONE JSON line on rank 0 (see the task contract) with `roofline` for the
-dominant kernel and `cpu_baseline` (the oracle's C port timed on this host).
+Prints ONE JSON line on rank 0 (see the task contract) with `ms_per_step`, `roofline`
+for the dominant kernel and `cpu_baseline` (the oracle's C port timed on this host).
+The line stays a few KB: the full secondary measurements go to bench_extra.json beside
+this file, their compact `extra_summary` into the line.  `--dump-outputs DIR` writes
+what the last timed step returned (states, actions, costs, status; a fixed sample of
+instances within 64 MB) as DIR/<name>.npy, float32, for comparing two builds.
 """
 
 import argparse
@@ -925,6 +929,39 @@ def extras_only(args):
     return 0
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: under 64 MB in all, .npy headers included
+DUMP_SEED = 0
+EXTRA_FILE = os.path.join(ROOT, "bench_extra.json")
+
+
+def _finite(v):
+    """NaN / inf -> None, recursively: the result line is strict JSON."""
+    if isinstance(v, float):
+        return v if np.isfinite(v) else None
+    if isinstance(v, dict):
+        return {k: _finite(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_finite(x) for x in v]
+    return v
+
+
+def dump_outputs(directory, states, actions, costs, status):
+    """What the timed path handed its caller in its last step, as DIR/<name>.npy (float32): every instance when the batch fits
+    the budget, else a fixed sample (default_rng(DUMP_SEED), sorted) of whole instances, the same sample in every run."""
+    B = states.shape[0]
+    per_instance = 4 * (states[0].numel() + actions[0].numel() + costs[0].numel() + 1)
+    keep = min(B, max(1, DUMP_BUDGET_BYTES // per_instance))
+    if keep < B:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=keep, replace=False))
+    else:
+        idx = np.arange(B)
+    sel = torch.from_numpy(idx).to(states.device)
+    os.makedirs(directory, exist_ok=True)
+    for name, t in (("states", states), ("actions", actions), ("costs", costs), ("status", status)):
+        np.save(os.path.join(directory, name + ".npy"), t.index_select(0, sel).cpu().numpy().astype(np.float32))
+    return {"dir": directory, "instances": int(keep), "of": int(B), "sample_seed": DUMP_SEED if keep < B else None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs of this node (default: WORLD_SIZE, else 1)")
@@ -943,7 +980,14 @@ def main():
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="TEST ONLY: no GPU work; a fixed-sleep stand-in step drives the multi-rank control flow "
                          "(barriers, MAX over ranks, the final gather) over gloo so it can be tested without GPUs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (states, actions, costs, status of a fixed "
+                         "sample of instances) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus is not None and args.gpus > 1:
             raise SystemExit(self_launch(args))         # before any GPU call in this process
@@ -1072,6 +1116,12 @@ def main():
         dist.all_reduce(kmax, op=dist.ReduceOp.MAX)
         kernel_ms = float(kmax.item())
 
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # (multi-GPU: the gathered global batch; one rank: its own shard, the last timed step's buffers)
+        res = gathered if gathered is not None else (out["states"], out["actions"], out["costs"], None, out["status"])
+        dumped = dump_outputs(args.dump_outputs, res[0], res[1], res[2], res[4])
+
     if rank == 0:
         total_solves = B_global * args.steps
         value = total_solves / elapsed
@@ -1136,11 +1186,23 @@ def main():
         if gather_error is not None:
             line["gather_error"] = gather_error
         if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(n, m, T)
+            try:
+                line["cpu_baseline"] = cpu_baseline(n, m, T)
+            except Exception as exc:                          # noqa: BLE001 -- a secondary number must never cost the headline line
+                line["cpu_baseline"] = {"error": repr(exc)[-600:]}
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if extras_child is not None:
-            line["extra"] = collect_extras(extras_child)
-            # the secondary numbers once more, compact and LAST in the line: a log that keeps only the tail of the line still shows them
-            line["extra_summary"] = summarise_extras(line["extra"])
+            extra = _finite(collect_extras(extras_child))
+            # the full secondary blocks go to a file beside bench.py, not into the line: the line stays a few KB (a 25 KB line was
+            # more than a driver that parses it would take); the compact summary stays LAST in the line
+            try:
+                with open(EXTRA_FILE, "w") as fh:
+                    json.dump(extra, fh, indent=1, allow_nan=False)
+                line["extra_file"] = os.path.basename(EXTRA_FILE)
+            except OSError as exc:
+                line["extra_file_error"] = repr(exc)
+            line["extra_summary"] = summarise_extras(extra)
         # five keys FIRST in the line (a log that keeps only the head of the line still shows them), the full blocks follow
         sx = line.get("extra_summary") or {}
         first = {"summary": {"headline_frac_of_fp32_peak": round(achieved / PEAK_F32_TFLOPS, 4),
@@ -1149,7 +1211,7 @@ def main():
                              "ilqr_api_warm_ms_frac": sx.get("ilqr_api_warm"),
                              "secondary_ms_frac": {k: sx.get(k) for k in ("cfg5_hvac", "cfg5_reservoir", "hvac6", "res4", "literal_dims") if k in sx}}}
         first.update(line)
-        print(json.dumps(first), flush=True)
+        print(json.dumps(_finite(first), allow_nan=False), flush=True)
 
     if use_dist:
         dist.barrier()

@@ -1,34 +1,77 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes loader for ``oracle/c/lqr_oracle.c``."""
 
 import ctypes
+import hashlib
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "_build", "liblqr_oracle.so")
+_NAME = "liblqr_oracle.so"
 _lib = None
 
 
+def _host():
+    """The library's stamp: the host CPU (``-march=native``) and the sources it was compiled from."""
+    info = open("/proc/cpuinfo").read() if os.path.exists("/proc/cpuinfo") else ""
+    cpu = info.split("model name")[1].split("\n")[0] if "model name" in info else ""
+    h = hashlib.sha256()
+    for name in ("lqr_oracle.c", "lqr_oracle_impl.h"):
+        with open(os.path.join(_HERE, "c", name), "rb") as fh:
+            h.update(fh.read())
+    return f"{cpu}\nsources {h.hexdigest()[:16]}"
+
+
+def _current(so, host):
+    stamp = so + ".host"
+    return os.path.exists(so) and os.path.exists(stamp) and open(stamp).read() == host
+
+
+def _writable(folder):
+    try:
+        os.makedirs(folder, exist_ok=True)
+        probe = os.path.join(folder, f".w{os.getpid()}")
+        open(probe, "w").close()
+        os.remove(probe)
+        return True
+    except OSError:
+        return False
+
+
+def _candidates(host):
+    """oracle/_build/ first; when the tree is not writable by this user, a per-user cache keyed by the host CPU."""
+    key = "lqr_oracle-" + hashlib.sha256(host.encode()).hexdigest()[:12]
+    user = os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "tfmpc", "oracle", key)
+    return [os.path.join(_HERE, "_build"), user, os.path.join(tempfile.gettempdir(), f"tfmpc-oracle-{os.getuid()}", key)]
+
+
 def build(force=False):
-    """Compile the C restatement (gcc, seconds).  ``-march=native`` is used, so
-    the library is rebuilt on the machine that runs it."""
-    stamp = _SO + ".host"
-    host = open("/proc/cpuinfo").read().split("model name")[1].split("\n")[0] if os.path.exists("/proc/cpuinfo") else ""
-    stale = force or not os.path.exists(_SO) or not os.path.exists(stamp) or open(stamp).read() != host
-    if stale:
-        subprocess.check_call(["make", "-s", "-B", "-C", _HERE, "_build/liblqr_oracle.so"])
-        with open(stamp, "w") as fh:
-            fh.write(host)
-    return _SO
+    """Compile the C restatement (gcc, seconds) and return the library's path.  ``-march=native`` is used, so
+    the library is rebuilt on a host with another CPU -- into oracle/_build/ when this user may write there,
+    else into a per-user cache."""
+    host = _host()
+    folders = _candidates(host)
+    if not force:
+        for folder in folders:
+            so = os.path.join(folder, _NAME)
+            if _current(so, host):
+                return so
+    for folder in folders:
+        if _writable(folder):
+            so = os.path.join(folder, _NAME)
+            subprocess.check_call(["make", "-s", "-B", "-C", _HERE, f"BUILD={folder}", so])
+            with open(so + ".host", "w") as fh:
+                fh.write(host)
+            return so
+    raise RuntimeError("oracle/c_oracle.py: no writable directory for the C restatement: " + ", ".join(folders))
 
 
 def _load():
     global _lib
     if _lib is None:
-        build()
-        _lib = ctypes.CDLL(_SO)
+        _lib = ctypes.CDLL(build())
     return _lib
 
 

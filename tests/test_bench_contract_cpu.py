@@ -111,3 +111,41 @@ def test_extra_summary_is_compact_and_survives_missing_entries():
         "bf16_storage_sweep": {"error": "x"}})
     assert full["ilqr_api_warm"] == [5.46, 0.357, 0.201] and full["cfg5_hvac"] == [13.1, 0.194, 0.429] and full["cfg4_one_launch_8x16384_Mit_s"] == 56.1
     assert full["bf16_sweep"] is None and len(json.dumps(full)) < 1200
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: float32 .npy files of the last step's outputs, whole instances, the same sample in every run, under 64 MB."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    B, n, m, T = 65536, 16, 8, 50
+    g = torch.Generator().manual_seed(0)
+    states, actions = torch.randn(B, T + 1, n, 1, generator=g), torch.randn(B, T, m, 1, generator=g)
+    costs, status = torch.randn(B, T + 1, 1, 1, generator=g), torch.zeros(B, dtype=torch.int32)
+    status[7] = 2
+    a = bench.dump_outputs(str(tmp_path / "a"), states, actions, costs, status)
+    b = bench.dump_outputs(str(tmp_path / "b"), states, actions, costs, status)
+    assert 0 < a["instances"] < B and a == dict(b, dir=a["dir"])
+    total = 0
+    for name in ("states", "actions", "costs", "status"):
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape[0] == a["instances"] and np.array_equal(x, y)
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert total <= 64 << 20
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(B, size=a["instances"], replace=False))
+    assert np.array_equal(np.load(tmp_path / "a" / "states.npy"), states[idx].numpy())
+    small = bench.dump_outputs(str(tmp_path / "c"), states[:100], actions[:100], costs[:100], status[:100])
+    assert small["instances"] == 100 and np.array_equal(np.load(tmp_path / "c" / "status.npy"), status[:100].numpy().astype(np.float32))
+
+
+def test_result_line_is_strict_json():
+    sys.path.insert(0, ROOT)
+    import bench
+    line = bench._finite({"a": float("nan"), "b": [1.0, float("inf")], "c": {"d": -float("inf"), "e": 2}})
+    assert json.loads(json.dumps(line, allow_nan=False)) == {"a": None, "b": [1.0, None], "c": {"d": None, "e": 2}}
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, "bench.py", "--dry-run-cpu", "--steps", "0"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--steps" in out.stderr

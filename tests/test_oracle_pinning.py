@@ -2,6 +2,7 @@
 reference itself holds for the hot path.  These mirror the
 reference's own tests; citations are into ``/root/reference/tests``."""
 
+import os
 import numpy as np
 import pytest
 
@@ -325,3 +326,19 @@ def test_vectorised_derivatives_equal_the_per_step_loop():
             for a, b, field in zip(fast, loop, fast._fields):
                 assert a.shape == b.shape, (type(env).__name__, name, field)
                 assert np.abs(a - b).max() <= 1e-12 * max(1.0, np.abs(b).max()), (type(env).__name__, name, field)
+
+
+def test_c_oracle_builds_elsewhere_when_its_folder_is_not_writable(tmp_path, monkeypatch):
+    """A tree this user may not write to (or a library stamped for another CPU) must not stop the C restatement from
+    loading: it is compiled into the next writable folder, stamped there, and found current on the next call."""
+    blocked = tmp_path / "file"
+    blocked.write_text("")
+    spare = tmp_path / "cache"
+    monkeypatch.setattr(c_oracle, "_candidates", lambda host: [str(blocked / "_build"), str(spare)])
+    so = c_oracle.build()
+    assert so == str(spare / "liblqr_oracle.so") and open(so + ".host").read() == c_oracle._host()
+    mtime = os.path.getmtime(so)
+    assert c_oracle.build() == so and os.path.getmtime(so) == mtime          # current: not compiled again
+    with open(so + ".host", "w") as fh:
+        fh.write("another cpu")
+    assert c_oracle.build() == so and open(so + ".host").read() == c_oracle._host()
