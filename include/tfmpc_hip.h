@@ -181,6 +181,42 @@ int tfmpc_lqr_solve_general_f32(int B, int n, int m, int T,
                                 int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
 
+/* ------------------------------------------------------- time-varying LQR --------
+ * TV-LQR: the problem above with a model per step.  For each instance b, z_t = [x_t; u_t], d = n + m:
+ *   x_{t+1} = F_t z_t + f_t,  F_t[n][d], f_t[n];  stage cost 1/2 z_t^T C_t z_t + c_t^T z_t,  C_t[d][d], c_t[d];
+ *   final cost 1/2 x_T^T C_fin x_T + c_fin^T x_T,  Cfin[n][n], cfin[n].
+ * Model operand X of instance b at step t is read at X + b * sX_b + t * sX_t (elements): sX_b = 0 shares it across
+ * the batch, sX_t = 0 holds it constant in time.  Cfin / cfin have a batch stride only; both NULL selects
+ * C_fin = C_{T-1}[:n,:n], c_fin = c_{T-1}[:n] (with every step equal: exactly tfmpc_lqr_*_f32's problem).
+ * T >= 1.  Backward: the recursion of tfmpc_lqr_backward_f32 with F_t, f_t, C_t, c_t at step t (const accumulates
+ * with f_t and the value function of step t+1).  Outputs, statuses and error codes as in the LQR block, including
+ * the PRECONDITION (C_t and C_fin symmetric, C_t,uu > 0: TFMPC_ST_NOT_PD / TFMPC_ST_SINGULAR per instance).
+ * n <= 16, m <= 8: the 16 x 8 matrix-core sweep (models streamed per step); larger shapes: a wave-per-instance
+ * fp32 kernel up to its LDS limit, TFMPC_ERR_UNSUPPORTED beyond.  B == 0 is a no-op. */
+size_t tfmpc_tvlqr_workspace_bytes(int B, int n, int m, int T);
+const char *tfmpc_tvlqr_kernel_name(int n, int m, int T);
+int tfmpc_tvlqr_backward_f32(int B, int n, int m, int T,
+                             const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                             const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+                             const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
+                             float *K, float *k, float *V, float *v, float *cst, int32_t *status, void *stream);
+/* K[B][T][m][n] with batch stride strideK (0 = one policy for the batch), k likewise. */
+int tfmpc_tvlqr_forward_f32(int B, int n, int m, int T,
+                            const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                            const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+                            const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
+                            const float *K, long strideK, const float *k, long stride_k,
+                            const float *x0, float *states, float *actions, float *costs, void *stream);
+/* Fused backward + forward; K, k, V, v, cst optional (if K or k is NULL, `workspace` must hold
+ * tfmpc_tvlqr_workspace_bytes(...) bytes). */
+int tfmpc_tvlqr_solve_f32(int B, int n, int m, int T,
+                          const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                          const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+                          const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
+                          const float *x0, float *states, float *actions, float *costs,
+                          float *K, float *k, float *V, float *v, float *cst, int32_t *status,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 /* --------------------------------------------------------------- iLQR --------
  * Control-limited iLQR (tfmpc/solvers/ilqr.py) over the reference's differentiable
  * environments (tfmpc/envs).  An environment is described by a kind tag plus

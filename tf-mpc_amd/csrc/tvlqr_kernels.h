@@ -1,0 +1,40 @@
+// tvlqr_kernels.h -- internal launch interface of the time-varying LQR kernels (tvlqr_mfma16x8.hip,
+// tvlqr_generic.hip) and their C-ABI dispatcher (tvlqr_dispatch.hip).  Not installed; the public contract
+// is the TV-LQR block of include/tfmpc_hip.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/tfmpc_hip.h"
+
+namespace tfmpc {
+
+// Model operand X of instance b at step t starts at X + b * sX_b + t * sX_t (elements; 0 = shared / constant).
+struct TvLqrArgs {
+    int B, n, m, T;
+    const float *F, *f, *C, *c;
+    long sF_b, sF_t, sf_b, sf_t, sC_b, sC_t, sc_b, sc_t;
+    const float *Cfin, *cfin;     // final cost [n][n], [n]; both NULL: C_{T-1}[:n,:n], c_{T-1}[:n]
+    long sCfin_b, scfin_b;
+    const float *x0;
+    float *K, *k;                 // [B][T][m][n], [B][T][m]
+    long sK, sk;                  // batch strides of K, k (forward-only launches may share a policy: 0)
+    float *V, *v, *cst;           // optional value-function outputs [B][T][n][n], [B][T][n], [B][T]
+    float *states, *actions, *costs;
+    int32_t *status;
+};
+
+__host__ __device__ inline const float *tv_at(const float *p, long sb, long st, int b, int t)
+{
+    return p + (size_t)b * sb + (size_t)t * st;
+}
+
+bool tvlqr_mfma_supported(int n, int m);
+int tvlqr_mfma_launch(const TvLqrArgs &a, bool backward, bool forward, hipStream_t stream);
+
+size_t tvlqr_generic_smem_bytes(int n, int m);
+int tvlqr_generic_launch(const TvLqrArgs &a, bool backward, bool forward, hipStream_t stream);
+
+}  // namespace tfmpc

@@ -42,6 +42,16 @@ _SIGNATURES = {
 }
 
 
+_TV_MODEL = [_I, _I, _I, _I] + [_P, _L, _L] * 4 + [_P, _L, _P, _L]      # B n m T, F f C c (+ batch, time strides), Cfin cfin
+_SIGNATURES.update({
+    "tfmpc_tvlqr_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "tfmpc_tvlqr_kernel_name": (ctypes.c_char_p, [_I, _I, _I]),
+    "tfmpc_tvlqr_backward_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P]),
+    "tfmpc_tvlqr_forward_f32": (_I, _TV_MODEL + [_P, _L, _P, _L, _P, _P, _P, _P, _P]),
+    "tfmpc_tvlqr_solve_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+})
+
+
 for _name in ("backward", "forward", "solve"):       # twins for a non-symmetric C (tfmpc_hip.h PRECONDITION)
     _SIGNATURES[f"tfmpc_lqr_{_name}_general_f32"] = _SIGNATURES[f"tfmpc_lqr_{_name}_f32"]
 
@@ -49,7 +59,7 @@ ENV_LQ, ENV_NAVLQR, ENV_NAVIGATION, ENV_HVAC, ENV_RESERVOIR, ENV_USER = range(6)
 ENV_MAX_PARAMS = 10
 MAX_ALPHAS = 16
 TRACE_COLS = 11          # TFMPC_TRACE_COLS
-MIN_VERSION = 310        # tfmpc_version() this binding was written against (include/tfmpc_hip.h)
+MIN_VERSION = 320        # tfmpc_version() this binding was written against (include/tfmpc_hip.h)
 
 
 class TfmpcEnv(ctypes.Structure):

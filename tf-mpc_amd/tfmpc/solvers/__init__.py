@@ -1,2 +1,4 @@
 """Solvers of the hot path: :mod:`tfmpc.solvers.lqr` (Riccati sweep + rollout) and :mod:`tfmpc.solvers.ilqr`
 (control-limited iLQR), both thin ctypes front ends of ``tfmpc/_lib/libtfmpc_hip.so``."""
+
+from tfmpc.solvers.tvlqr import TimeVaryingLQR  # noqa: E402,F401  (time-varying LQR, tfmpc_tvlqr_*_f32)

@@ -1,0 +1,262 @@
+"""Time-varying batched LQR on MI355X (``tfmpc_tvlqr_*_f32``, include/tfmpc_hip.h).
+
+The problem of :class:`tfmpc.solvers.lqr.LQR` with a model per step: ``x_{t+1} = F_t z_t + f_t``, stage cost
+``1/2 z_t^T C_t z_t + c_t^T z_t`` with ``z_t = [x_t; u_t]``, final cost ``1/2 x_T^T C_fin x_T + c_fin^T x_T``
+(default ``C_fin = C_{T-1}[:n,:n]``, ``c_fin = c_{T-1}[:n]``: with every step equal this is exactly ``LQR``'s problem).
+
+Operand shapes: ``F`` is ``[T, n, d]`` (shared by the batch) or ``[B, T, n, d]``; ``f``, ``C``, ``c`` likewise
+(vectors as ``[..., size]`` or columns ``[..., size, 1]``).  A time axis of size 1 is broadcast over the horizon with
+time stride 0 (no copy).  ``C_final`` is ``[n, n]`` or ``[B, n, n]``, ``c_final`` ``[n]`` / ``[n, 1]`` / ``[B, n(, 1)]``.
+``C_t`` and ``C_final`` must be symmetric (the kernels' precondition; there is no general-C path).
+"""
+
+import numpy as np
+import torch
+
+from tfmpc import _hip
+from tfmpc.solvers.lqr import LQR, Policy, ValueFn, _as_f32
+from tfmpc.utils import trajectory
+
+
+def _is_symmetric(t):
+    if t.numel() == 0:
+        return True
+    return bool((t - t.transpose(-1, -2)).abs().amax() <= 1e-6 * t.abs().amax())
+
+
+class TimeVaryingLQR:
+
+    def __init__(self, F, f, C, c, C_final=None, c_final=None, device=None, symmetric=None):
+        """``symmetric``: ``None`` checks ``C`` (and ``C_final``) once on the device; ``True`` states it and skips the
+        check (no synchronisation); ``False`` raises -- only symmetric costs are served."""
+        self.device = torch.device(device) if device is not None else _hip.default_device()
+        F, f, C, c = (_as_f32(a, self.device) for a in (F, f, C, c))
+        if F.dim() not in (3, 4):
+            raise ValueError(f"F must be [T, n, d] or [B, T, n, d], got {tuple(F.shape)}")
+        n, d = F.shape[-2], F.shape[-1]
+        if not (0 < n < d):
+            raise ValueError(f"F must end in [n, n+m] with m > 0, got {tuple(F.shape)}")
+        f, c = self._vector(f, n, "f"), self._vector(c, d, "c")
+        if C.dim() not in (3, 4) or tuple(C.shape[-2:]) != (d, d):
+            raise ValueError(f"C must be [T, d, d] or [B, T, d, d] with d={d}, got {tuple(C.shape)}")
+        ops = [F, f, C, c]
+        horizons = {t.shape[-3] for t in ops if t.shape[-3] != 1}
+        if len(horizons) > 1:
+            raise ValueError(f"time axes disagree: {sorted(horizons)} (each must be 1 or the horizon T)")
+        self.horizon = horizons.pop() if horizons else 1
+        if self.horizon < 1:
+            raise ValueError("the horizon must be at least 1 step")
+        batches = {t.shape[0] for t in ops if t.dim() == 4}
+        if (C_final is None) != (c_final is None):
+            raise ValueError("give both C_final and c_final, or neither")
+        if C_final is not None:
+            C_final, c_final = _as_f32(C_final, self.device), _as_f32(c_final, self.device)
+            if C_final.dim() not in (2, 3) or tuple(C_final.shape[-2:]) != (n, n):
+                raise ValueError(f"C_final must be [n, n] or [B, n, n] with n={n}, got {tuple(C_final.shape)}")
+            if c_final.dim() == 1 or (c_final.dim() == 2 and c_final.shape != (n, 1)):
+                c_final = c_final.unsqueeze(-1)
+            if tuple(c_final.shape[-2:]) != (n, 1) or c_final.dim() not in (2, 3):
+                raise ValueError(f"c_final must be [n], [n, 1], [B, n] or [B, n, 1] with n={n}, got {tuple(c_final.shape)}")
+            batches |= {t.shape[0] for t in (C_final, c_final) if t.dim() == 3}
+            C_final, c_final = C_final.contiguous(), c_final.contiguous()
+        if len(batches) > 1:
+            raise ValueError(f"batch axes disagree: {sorted(batches)}")
+        self.batch_size = batches.pop() if batches else None
+        self.F, self.f, self.C, self.c = (self._inner_contiguous(t) for t in ops)
+        self.C_final, self.c_final = C_final, c_final
+        self.last_status = None
+        if symmetric is None:
+            symmetric = _is_symmetric(self.C) and (C_final is None or _is_symmetric(C_final))
+        if not symmetric:
+            raise ValueError("C (and C_final) must be symmetric: the time-varying kernels serve symmetric costs only")
+
+    @staticmethod
+    def _vector(t, size, name):
+        """``[(B,)T, size]`` or ``[(B,)T, size, 1]`` -> ``[(B,)T, size, 1]``."""
+        if t.dim() >= 3 and t.shape[-1] == 1 and t.shape[-2] == size:
+            out = t
+        else:
+            out = t.unsqueeze(-1)
+        if out.dim() not in (3, 4) or out.shape[-2] != size:
+            raise ValueError(f"{name} must be [T, {size}] / [T, {size}, 1] (or with a leading batch axis), got {tuple(t.shape)}")
+        return out
+
+    @staticmethod
+    def _inner_contiguous(t):
+        """Keep views whose per-step matrix is dense row-major (e.g. a time axis expanded with stride 0)."""
+        r, cols = t.shape[-2], t.shape[-1]
+        if (t.stride(-1) == 1 or cols == 1) and (t.stride(-2) == cols or r == 1):
+            return t
+        return t.contiguous()
+
+    @classmethod
+    def from_lqr(cls, lqr, T):
+        """The time-invariant problem of ``lqr`` over ``T`` steps as a TV problem: views with time stride 0."""
+        T = int(T)
+        views = [t.unsqueeze(-3).expand(*t.shape[:-2], T, *t.shape[-2:]) for t in (lqr.F, lqr.f, lqr.C, lqr.c)]
+        if not lqr.symmetric_cost:
+            raise ValueError("only a symmetric C has a time-varying counterpart")
+        return cls(*views, device=lqr.device, symmetric=True)
+
+    # -- properties ----------------------------------------------------------------
+    @property
+    def n_dim(self):
+        return self.F.shape[-1]
+
+    @property
+    def state_size(self):
+        return self.F.shape[-2]
+
+    @property
+    def action_size(self):
+        return self.n_dim - self.state_size
+
+    # -- per-step model (plain tensor ops, not the hot path) -------------------------
+    def _step(self, t_op, t):
+        return t_op.select(-3, t if t_op.shape[-3] > 1 else 0)
+
+    def transition(self, x, u, t):
+        z = torch.cat([_as_f32(x, self.device), _as_f32(u, self.device)], dim=-2)
+        return self._step(self.F, t) @ z + self._step(self.f, t)
+
+    def cost(self, x, u, t):
+        z = torch.cat([_as_f32(x, self.device), _as_f32(u, self.device)], dim=-2)
+        zt = z.transpose(-1, -2)
+        return 0.5 * (zt @ self._step(self.C, t)) @ z + zt @ self._step(self.c, t)
+
+    def final_cost(self, x):
+        x = _as_f32(x, self.device)
+        n = self.state_size
+        if self.C_final is not None:
+            Cf, cf = self.C_final, self.c_final
+        else:
+            T = self.horizon
+            Cf, cf = self._step(self.C, T - 1)[..., :n, :n], self._step(self.c, T - 1)[..., :n, :]
+        xt = x.transpose(-1, -2)
+        return 0.5 * (xt @ Cf) @ x + xt @ cf
+
+    # -- helpers -----------------------------------------------------------------------
+    def _model_args(self):
+        args = []
+        for t in (self.F, self.f, self.C, self.c):
+            sb = t.stride(0) if t.dim() == 4 else 0
+            st = t.stride(-3) if t.shape[-3] > 1 else 0
+            args += [_hip.ptr(t), sb, st]
+        if self.C_final is None:
+            args += [None, 0, None, 0]
+        else:
+            args += [_hip.ptr(self.C_final), self.C_final.stride(0) if self.C_final.dim() == 3 else 0,
+                     _hip.ptr(self.c_final), self.c_final.stride(0) if self.c_final.dim() == 3 else 0]
+        return args
+
+    def _prep_x0(self, x0):
+        return LQR._prep_x0(self, x0)
+
+    def _resolve_batch(self, x0=None):
+        return LQR._resolve_batch(self, x0)
+
+    # -- backward / forward / solve ------------------------------------------------------
+    def backward(self):
+        lib = _hip.require_gpu()
+        n, m, T = self.state_size, self.action_size, self.horizon
+        B = self.batch_size
+        Bk = B if B is not None else 1
+        dev = self.device
+        K = torch.empty((Bk, T, m, n), device=dev)
+        k = torch.empty((Bk, T, m, 1), device=dev)
+        V = torch.empty((Bk, T, n, n), device=dev)
+        v = torch.empty((Bk, T, n, 1), device=dev)
+        const = torch.empty((Bk, T, 1, 1), device=dev)
+        status = torch.zeros((Bk,), dtype=torch.int32, device=dev)
+        rc = lib.tfmpc_tvlqr_backward_f32(Bk, n, m, T, *self._model_args(), _hip.ptr(K), _hip.ptr(k), _hip.ptr(V),
+                                          _hip.ptr(v), _hip.ptr(const), _hip.ptr(status), _hip.stream())
+        _hip.check(rc, "tfmpc_tvlqr_backward_f32")
+        self.last_status = status
+        if B is None:
+            K, k, V, v, const = K[0], k[0], V[0], v[0], const[0]
+        return Policy(K, k), ValueFn(V, v, const)
+
+    def forward(self, policy, x0):
+        lib = _hip.require_gpu()
+        n, m, T = self.state_size, self.action_size, self.horizon
+        x0 = self._prep_x0(x0)
+        if isinstance(policy, Policy):
+            K, k = policy.K, policy.k
+        else:
+            tdim = _as_f32(policy[0][0], self.device).dim() - 2
+            K = torch.stack([_as_f32(p[0], self.device) for p in policy], dim=tdim)
+            k = torch.stack([_as_f32(p[1], self.device) for p in policy], dim=tdim)
+        K, k = K.contiguous(), k.contiguous()
+        if K.shape[-3] < T:
+            raise ValueError(f"policy has {K.shape[-3]} steps, horizon is {T}")
+        if K.shape[-3] != T:            # the kernels read K[b][t] at b * T * m * n + t * m * n
+            K, k = K.narrow(-3, 0, T).contiguous(), k.narrow(-3, 0, T).contiguous()
+        pol_batched = K.dim() == 4
+        B = self._resolve_batch(x0)
+        if pol_batched:
+            if B is not None and K.shape[0] != B:
+                raise ValueError("policy batch does not match")
+            B = K.shape[0]
+        Bk = B if B is not None else 1
+        if x0.dim() == 2:
+            x0 = x0.unsqueeze(0).expand(Bk, n, 1).contiguous()
+        dev = self.device
+        states = torch.empty((Bk, T + 1, n, 1), device=dev)
+        actions = torch.empty((Bk, T, m, 1), device=dev)
+        costs = torch.empty((Bk, T + 1, 1, 1), device=dev)
+        sK = K[0].numel() if pol_batched else 0
+        sk = k[0].numel() if pol_batched else 0
+        rc = lib.tfmpc_tvlqr_forward_f32(Bk, n, m, T, *self._model_args(), _hip.ptr(K), sK, _hip.ptr(k), sk,
+                                         _hip.ptr(x0), _hip.ptr(states), _hip.ptr(actions), _hip.ptr(costs), _hip.stream())
+        _hip.check(rc, "tfmpc_tvlqr_forward_f32")
+        if B is None:
+            states, actions, costs = states[0], actions[0], costs[0]
+        return states, actions, costs
+
+    def solve_device(self, x0, want_policy=False, want_value=False, workspace=None):
+        """One kernel launch for ``B`` solves; a dict of device tensors shaped like ``LQR.solve_device``'s
+        (``states[B,T+1,n,1]``, ``actions[B,T,m,1]``, ``costs[B,T+1,1,1]``, ``status[B]``, on request
+        ``K, k, V, v, const``).  Never synchronises."""
+        lib = _hip.require_gpu()
+        n, m, T = self.state_size, self.action_size, self.horizon
+        x0 = self._prep_x0(x0)
+        B = self._resolve_batch(x0)
+        Bk = B if B is not None else 1
+        if x0.dim() == 2:
+            x0 = x0.unsqueeze(0).expand(Bk, n, 1).contiguous()
+        dev = self.device
+        out = dict(states=torch.empty((Bk, T + 1, n, 1), device=dev),
+                   actions=torch.empty((Bk, T, m, 1), device=dev),
+                   costs=torch.empty((Bk, T + 1, 1, 1), device=dev),
+                   status=(torch.zeros if Bk == 0 else torch.empty)((Bk,), dtype=torch.int32, device=dev))
+        if want_policy:
+            out.update(K=torch.empty((Bk, T, m, n), device=dev), k=torch.empty((Bk, T, m, 1), device=dev))
+        if want_value:
+            out.update(V=torch.empty((Bk, T, n, n), device=dev), v=torch.empty((Bk, T, n, 1), device=dev),
+                       const=torch.empty((Bk, T, 1, 1), device=dev))
+        ws_bytes = 0
+        if not want_policy:
+            ws_bytes = int(lib.tfmpc_tvlqr_workspace_bytes(Bk, n, m, T))
+            if workspace is None or workspace.numel() * workspace.element_size() < ws_bytes:
+                workspace = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
+            ws_bytes = workspace.numel() * workspace.element_size()
+        rc = lib.tfmpc_tvlqr_solve_f32(Bk, n, m, T, *self._model_args(), _hip.ptr(x0),
+                                       _hip.ptr(out["states"]), _hip.ptr(out["actions"]), _hip.ptr(out["costs"]),
+                                       _hip.ptr(out.get("K")), _hip.ptr(out.get("k")), _hip.ptr(out.get("V")),
+                                       _hip.ptr(out.get("v")), _hip.ptr(out.get("const")), _hip.ptr(out["status"]),
+                                       _hip.ptr(workspace), ws_bytes, _hip.stream())
+        _hip.check(rc, "tfmpc_tvlqr_solve_f32")
+        self.last_status = out["status"]
+        out["batched"] = B is not None
+        out["workspace"] = workspace
+        return out
+
+    def solve(self, x0):
+        out = self.solve_device(x0)
+        states, actions, costs = out["states"], out["actions"], out["costs"]
+        if not out["batched"]:
+            states, actions, costs = states[0], actions[0], costs[0]
+        return trajectory.Trajectory(states, actions, costs)
+
+
+__all__ = ["TimeVaryingLQR"]
