@@ -217,6 +217,30 @@ int tfmpc_tvlqr_solve_f32(int B, int n, int m, int T,
                           float *K, float *k, float *V, float *v, float *cst, int32_t *status,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------ TV-LQR gradients --------
+ * Vector-Jacobian product of tfmpc_tvlqr_solve_f32: given the forward's states[B][T+1][n] (states[b][0]
+ * is x0) and actions[B][T][m], and upstream gradients g_states[B][T+1][n], g_actions[B][T][m], g_costs[B][T+1] (each
+ * NULL = zero), writes the gradients of sum(g_states * states) + sum(g_actions * actions) + sum(g_costs * costs) with
+ * respect to F, f, C, c, Cfin, cfin and x0.  Model operands and their strides as in tfmpc_tvlqr_solve_f32 (Cfin = cfin =
+ * NULL: the default final cost, whose gradient then lands in dC[T-1][:n,:n] and dc[T-1][:n]; dCfin / dcfin must be NULL).
+ * Every output has its own batch and time stride in elements (dCfin, dcfin, dx0: batch only); a stride of 0 SUMS the
+ * gradient over that axis.  A NULL output is not computed.  C and Cfin enter as symmetric matrices, so dC and dCfin are
+ * the symmetric gradients.  The reductions run in a fixed order without atomics: repeated calls give identical bits.
+ * status[B] (required) gets the adjoint solve's status; an instance with TFMPC_ST_NOT_PD or TFMPC_ST_SINGULAR has NaN
+ * in its own gradient rows and in every batch-summed gradient.  workspace must hold
+ * tfmpc_tvlqr_vjp_workspace_bytes(B, n, m, T) bytes.  Shapes as the solve serves; B == 0 is a no-op. */
+size_t tfmpc_tvlqr_vjp_workspace_bytes(int B, int n, int m, int T);
+int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
+                        const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                        const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+                        const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
+                        const float *states, const float *actions,
+                        const float *g_states, const float *g_actions, const float *g_costs,
+                        float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t,
+                        float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
+                        float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
+                        int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* --------------------------------------------------------------- iLQR --------
  * Control-limited iLQR (tfmpc/solvers/ilqr.py) over the reference's differentiable
  * environments (tfmpc/envs).  An environment is described by a kind tag plus

@@ -49,6 +49,9 @@ _SIGNATURES.update({
     "tfmpc_tvlqr_backward_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P]),
     "tfmpc_tvlqr_forward_f32": (_I, _TV_MODEL + [_P, _L, _P, _L, _P, _P, _P, _P, _P]),
     "tfmpc_tvlqr_solve_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "tfmpc_tvlqr_vjp_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    # states actions, g_states g_actions g_costs, dF df dC dc (+ batch, time strides), dCfin dcfin dx0 (+ batch stride)
+    "tfmpc_tvlqr_vjp_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3 + [_P, _P, _Z, _P]),
 })
 
 

@@ -2,3 +2,4 @@
 (control-limited iLQR), both thin ctypes front ends of ``tfmpc/_lib/libtfmpc_hip.so``."""
 
 from tfmpc.solvers.tvlqr import TimeVaryingLQR  # noqa: E402,F401  (time-varying LQR, tfmpc_tvlqr_*_f32)
+from tfmpc.solvers.tvlqr_grad import tvlqr_solve  # noqa: E402,F401  (differentiable TV-LQR solve, tfmpc_tvlqr_vjp_f32)

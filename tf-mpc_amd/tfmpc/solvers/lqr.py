@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from tfmpc import _hip
+from tfmpc.solvers import tvlqr_grad
 from tfmpc.utils import trajectory
 
 
@@ -68,6 +69,10 @@ class LQR:
         include/tfmpc_hip.h -- which costs two temporaries and a host read-back; ``True`` / ``False`` states it and
         skips the check (construction is then free of synchronisation, e.g. inside a stream capture)."""
         self.device = torch.device(device) if device is not None else _hip.default_device()
+        # the caller's TENSOR operands (a reference that keeps them alive with the solver), where the differentiable
+        # solve starts; numpy operands cannot require grad (None)
+        self._sources = tuple(a if isinstance(a, torch.Tensor) else None for a in (F, f, C, c))
+        self.last_grad_status = None
         F, f, C, c = (_as_f32(a, self.device) for a in (F, f, C, c))
         n, d = F.shape[-2], F.shape[-1]
         f, c = _as_column(f, n), _as_column(c, d)
@@ -263,11 +268,31 @@ class LQR:
 
     # -- lqr.py:163-166 ------------------------------------------------------------
     def solve(self, x0, T):
+        if tvlqr_grad.wants_grad(*self._sources, x0):
+            return tvlqr_grad.TensorTrajectory(*self._solve_differentiable(x0, T))
         out = self.solve_device(x0, T)
         states, actions, costs = out["states"], out["actions"], out["costs"]
         if not out["batched"]:
             states, actions, costs = states[0], actions[0], costs[0]
         return trajectory.Trajectory(states, actions, costs)
+
+    def _solve_differentiable(self, x0, T):
+        """This class's own solve kernel forward (the same bits as without grad); backward through
+        ``tfmpc_tvlqr_vjp_f32`` with time stride 0, i.e. gradients summed over the horizon (tfmpc/solvers/tvlqr_grad.py)."""
+        if not self.symmetric_cost:
+            raise NotImplementedError("gradients of an LQR solve are served for a symmetric C only")
+        from tfmpc.solvers.tvlqr import TimeVaryingLQR
+        T = int(T)
+        n, d = self.state_size, self.n_dim
+        F, f, C, c = (own if a is None else tvlqr_grad.as_f32_graph(a, self.device)
+                      for a, own in zip(self._sources, (self.F, self.f, self.C, self.c)))
+        f, c = _as_column(f, n), _as_column(c, d)
+        x0g = _as_column(tvlqr_grad.as_f32_graph(x0, self.device), n)
+        problem = tvlqr_grad.Problem(lambda x: self.solve_device(x, T), lambda: TimeVaryingLQR.from_lqr(self, T), False, self)
+        states, actions, costs = tvlqr_grad.SolveFunction.apply(problem, x0g, F, f, C, c, None, None)
+        if self._resolve_batch(x0g) is None:
+            states, actions, costs = states[0], actions[0], costs[0]
+        return states, actions, costs
 
     # -- lqr.py:168-181 ------------------------------------------------------------
     def dump(self, file):

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from tfmpc import _hip
-from tfmpc.solvers.lqr import LQR, Policy, ValueFn, _as_f32
+from tfmpc.solvers import tvlqr_grad
+from tfmpc.solvers.lqr import LQR, Policy, ValueFn, _as_column, _as_f32
 from tfmpc.utils import trajectory
 
 
@@ -30,6 +31,11 @@ class TimeVaryingLQR:
         """``symmetric``: ``None`` checks ``C`` (and ``C_final``) once on the device; ``True`` states it and skips the
         check (no synchronisation); ``False`` raises -- only symmetric costs are served."""
         self.device = torch.device(device) if device is not None else _hip.default_device()
+        # The caller's TENSOR operands, where the differentiable path starts (numpy operands cannot require grad: None).
+        # A reference, not a copy -- but it keeps them alive as long as the solver, e.g. an fp64 / CPU original of a
+        # large per-instance model next to its fp32 device copy; drop the solver (or the originals) to free them.
+        self._sources = tuple(a if isinstance(a, torch.Tensor) else None for a in (F, f, C, c, C_final, c_final))
+        self.last_grad_status = None
         F, f, C, c = (_as_f32(a, self.device) for a in (F, f, C, c))
         if F.dim() not in (3, 4):
             raise ValueError(f"F must be [T, n, d] or [B, T, n, d], got {tuple(F.shape)}")
@@ -252,11 +258,44 @@ class TimeVaryingLQR:
         return out
 
     def solve(self, x0):
+        """A :class:`Trajectory`; with autograd recording and an operand or ``x0`` requiring grad, a
+        :class:`~tfmpc.solvers.tvlqr_grad.TensorTrajectory` differentiable through ``tfmpc_tvlqr_vjp_f32``."""
+        if tvlqr_grad.wants_grad(*self._sources, x0):
+            states, actions, costs = self.solve_tensors(x0)
+            return tvlqr_grad.TensorTrajectory(states, actions, costs)
         out = self.solve_device(x0)
         states, actions, costs = out["states"], out["actions"], out["costs"]
         if not out["batched"]:
             states, actions, costs = states[0], actions[0], costs[0]
         return trajectory.Trajectory(states, actions, costs)
+
+    def solve_tensors(self, x0):
+        """``(states[(B,)T+1,n,1], actions[(B,)T,m,1], costs[(B,)T+1,1,1])`` as tensors; in the autograd graph of the
+        caller's operands and ``x0`` when autograd is recording (gradients: tfmpc/solvers/tvlqr_grad.py)."""
+        if not tvlqr_grad.wants_grad(*self._sources, x0):
+            out = self.solve_device(x0)
+            states, actions, costs = out["states"], out["actions"], out["costs"]
+        else:
+            n, d = self.state_size, self.n_dim
+            dev = self.device
+            src = self._sources
+
+            def op(i, own, shape=None):       # a non-tensor operand needs no grad: its fp32 copy, already shaped
+                if src[i] is None:
+                    return own
+                t = tvlqr_grad.as_f32_graph(src[i], dev)
+                return shape(t) if shape else t
+            F, C = op(0, self.F), op(2, self.C)
+            f = op(1, self.f, lambda t: self._vector(t, n, "f"))
+            c = op(3, self.c, lambda t: self._vector(t, d, "c"))
+            Cf = op(4, self.C_final)
+            cf = op(5, self.c_final, lambda t: t.unsqueeze(-1) if t.dim() == 1 or (t.dim() == 2 and t.shape != (n, 1)) else t)
+            x0g = _as_column(tvlqr_grad.as_f32_graph(x0, dev), n)
+            problem = tvlqr_grad.Problem(lambda x: self.solve_device(x), lambda: self, True, self)
+            states, actions, costs = tvlqr_grad.SolveFunction.apply(problem, x0g, F, f, C, c, Cf, cf)
+        if self._resolve_batch(self._prep_x0(x0.detach() if isinstance(x0, torch.Tensor) else x0)) is None:
+            states, actions, costs = states[0], actions[0], costs[0]
+        return states, actions, costs
 
 
 __all__ = ["TimeVaryingLQR"]

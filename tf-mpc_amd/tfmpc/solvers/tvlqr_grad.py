@@ -1,0 +1,155 @@
+"""Differentiable LQR solves: a ``torch.autograd.Function`` over ``tfmpc_tvlqr_solve_f32`` (or ``LQR``'s own solve) and
+``tfmpc_tvlqr_vjp_f32`` (include/tfmpc_hip.h).
+
+The backward pass is one more time-varying LQR solve (the adjoint) plus a costate sweep; it needs the forward
+trajectory only, which is what the Function saves.  Each gradient has the shape of its operand: an operand without a
+batch axis (shared by the batch) gets the gradient summed over the batch, a time axis of size 1 (or an ``LQR``
+operand, which has none) the gradient summed over time.
+
+``C`` and ``C_final`` enter the kernels only as symmetric matrices, so their gradients are the symmetric ones: an fp64
+autograd oracle through a general-matrix recursion matches after ``(G + G^T) / 2``.  An instance whose solve is not
+positive definite gets NaN in its own gradient rows and in every gradient summed over a batch that contains it
+(``last_grad_status`` on the solver holds the per-instance status of the backward pass).  Double backward is not
+supported.
+"""
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from tfmpc import _hip
+from tfmpc.utils import trajectory
+
+
+def wants_grad(*operands):
+    """True when autograd is recording and some operand is a tensor that requires grad."""
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in operands)
+
+
+def as_f32_graph(a, device):
+    """Like ``lqr._as_f32`` but without ``detach``: a dtype / device conversion stays in the autograd graph."""
+    if isinstance(a, torch.Tensor):
+        return a.to(device=device, dtype=torch.float32)
+    return torch.as_tensor(np.asarray(a, dtype=np.float32), device=device)
+
+
+class Problem:
+    """What the Function needs besides tensors: ``run(x0)`` -> the forward's ``solve_device`` dict (batched outputs),
+    ``model()`` -> the :class:`TimeVaryingLQR` whose ``_model_args`` the VJP reads, ``timed`` (operands carry a time
+    axis) and ``owner`` (receives ``last_grad_status``)."""
+
+    def __init__(self, run, model, timed, owner):
+        self.run, self.model, self.timed, self.owner = run, model, timed, owner
+
+
+def _strides(g, ndim_batched, timed):
+    """(batch stride, time stride) of a contiguous gradient buffer ``g``; 0 = summed over that axis."""
+    batched = g.dim() == ndim_batched
+    sb = g[0].numel() if batched and g.shape[0] > 0 else 0
+    st = 0
+    if timed and g.shape[-3] > 1:
+        st = g.shape[-2] * g.shape[-1]
+    return sb, st
+
+
+class SolveFunction(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, problem, x0, F, f, C, c, C_final, c_final):
+        out = problem.run(x0.detach())
+        states, actions = out["states"], out["actions"]
+        ctx.problem = problem
+        ctx.meta = [(t.shape if t is not None else None) for t in (x0, F, f, C, c, C_final, c_final)]
+        ctx.save_for_backward(states, actions)
+        return states, out["actions"], out["costs"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_states, g_actions, g_costs):
+        states, actions = ctx.saved_tensors
+        problem = ctx.problem
+        tv = problem.model()
+        lib = _hip.require_gpu()
+        Bk, T1, n = states.shape[0], states.shape[1], states.shape[2]
+        T, m = T1 - 1, actions.shape[2]
+        dev = states.device
+        need = ctx.needs_input_grad
+        shapes = ctx.meta
+        nd_model = 4 if problem.timed else 3
+        alloc = torch.zeros if Bk == 0 else torch.empty
+        grads = [alloc(shapes[i], device=dev) if need[i + 1] and shapes[i] is not None else None for i in range(7)]
+        gx0, gF, gf, gC, gc, gCf, gcf = grads
+        args = []
+        for g in (gF, gf, gC, gc):
+            args += [_hip.ptr(g), *(_strides(g, nd_model, problem.timed) if g is not None else (0, 0))]
+        for g in (gCf, gcf, gx0):
+            args += [_hip.ptr(g), _strides(g, 3, False)[0] if g is not None else 0]
+        ups = [None if g is None else g.to(torch.float32).contiguous() for g in (g_states, g_actions, g_costs)]
+        status = torch.zeros((Bk,), dtype=torch.int32, device=dev)
+        ws_bytes = int(lib.tfmpc_tvlqr_vjp_workspace_bytes(Bk, n, m, T))
+        ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
+        rc = lib.tfmpc_tvlqr_vjp_f32(Bk, n, m, T, *tv._model_args(), _hip.ptr(states), _hip.ptr(actions),
+                                     *(_hip.ptr(u) for u in ups), *args, _hip.ptr(status), _hip.ptr(ws),
+                                     ws.numel() * 4, _hip.stream())
+        _hip.check(rc, "tfmpc_tvlqr_vjp_f32")
+        problem.owner.last_grad_status = status
+        return (None, gx0, gF, gf, gC, gc, gCf, gcf)
+
+
+class TensorTrajectory(trajectory.Trajectory):
+    """The :class:`~tfmpc.utils.trajectory.Trajectory` a differentiable ``solve`` returns: the same shapes and
+    properties, but ``states``, ``actions`` and ``costs`` stay torch tensors in the autograd graph."""
+
+    def __init__(self, states, actions, costs):
+        self.states = states.squeeze(-1) if states.shape[-1] == 1 else states
+        self.actions = actions.squeeze(-1) if actions.shape[-1] == 1 else actions
+        while costs.dim() > self.states.dim() - 1 and costs.shape[-1] == 1:
+            costs = costs.squeeze(-1)
+        self.costs = costs
+
+    @property
+    def batched(self):
+        return self.states.dim() == 3
+
+    @property
+    def total_cost(self):
+        return self.costs.sum(-1)
+
+    @property
+    def cumulative_cost(self):
+        return self.costs.cumsum(-1)
+
+    @property
+    def cost_to_go(self):
+        return self.costs.flip(-1).cumsum(-1).flip(-1)
+
+    def instance(self, b):
+        if not self.batched:
+            raise IndexError("not a batched trajectory")
+        return TensorTrajectory(self.states[b], self.actions[b], self.costs[b])
+
+    def detached(self):
+        """The plain numpy :class:`Trajectory` of the same values."""
+        return trajectory.Trajectory(self.states.detach()[..., None], self.actions.detach()[..., None], self.costs.detach())
+
+    def __repr__(self):
+        return "Tensor" + repr(self.detached())
+
+    def __str__(self):
+        return str(self.detached())
+
+    def save(self, filepath):
+        self.detached().save(filepath)
+
+
+def tvlqr_solve(F, f, C, c, x0, C_final=None, c_final=None):
+    """Solve the time-varying LQR of :class:`tfmpc.solvers.TimeVaryingLQR` (same operand shapes) from ``x0`` and
+    return ``(states, actions, costs)`` as tensors -- ``states[(B,)T+1,n,1]``, ``actions[(B,)T,m,1]``,
+    ``costs[(B,)T+1,1,1]`` -- differentiable with respect to every tensor operand and ``x0`` that requires grad."""
+    from tfmpc.solvers.tvlqr import TimeVaryingLQR
+    device = next((t.device for t in (F, f, C, c, x0) if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
+    tv = TimeVaryingLQR(F, f, C, c, C_final, c_final, device=device)
+    return tv.solve_tensors(x0)
+
+
+__all__ = ["SolveFunction", "TensorTrajectory", "tvlqr_solve"]
