@@ -45,6 +45,8 @@ extern "C" {
                                          optimization.py:47-51 does: x and free are those at the break.  (Inside iLQR the QP starts at the box
                                          centre, ilqr.py:369, where every coordinate is free: the first factorisation is of the whole H, and a
                                          positive definite H has no indefinite principal block -- the case needs a boundary start or rounding.) */
+#define TFMPC_ST_NOT_STABILISING 0x80 /* tfmpc_lqr_steady_state_f32: the doubling hit its cap, A_k did not go to zero, or a
+                                          non-finite value appeared: no stabilising solution was found */
 
 /* Library / device information ------------------------------------------------ */
 int tfmpc_version(void);
@@ -240,6 +242,26 @@ int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
                         float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
                         float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
                         int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------- infinite-horizon LQR --------
+ * The stationary solution of tfmpc_lqr_*_f32's problem: A = F[:, :n], B = F[:, n:], Q = C_xx,
+ * S = C_xu, R = C_uu (C symmetric).  P is the stabilising solution of the discrete algebraic Riccati equation, found by
+ * the structure-preserving doubling algorithm; then K = -(R + B'PB)^-1 (B'PA + S'), A_cl = A + BK,
+ * p = (I - A_cl')^-1 (c_x + K'c_u + A_cl'Pf), k = -(R + B'PB)^-1 (c_u + B'(Pf + p)): the limits of the finite
+ * recursion's K_t, k_t, V_t, v_t.  Outputs K[B][m][n], k[B][m], P[B][n][n], p[B][n] (each may be NULL),
+ * iterations[B] (doubling steps taken, optional), status[B] (required).  Batch strides in elements, 0 = shared.
+ * max_iter = 0 / tol = 0.0f select the defaults: 40 doubling steps, and a stop when max|H_{k+1} - H_k| <= tol max|H_{k+1}|
+ * with tol = 4 FLT_EPSILON (and max|A_{k+1}| <= 1e-3).  status: TFMPC_ST_NOT_PD (R or R + B'PB not positive definite),
+ * TFMPC_ST_SINGULAR (a zero pivot in I + GH or I - A_cl'), TFMPC_ST_NOT_STABILISING; a flagged instance gets NaN in its
+ * own outputs, no other instance is affected.  n <= 16, m <= 16: one wave per instance, products on the f32 matrix cores;
+ * n <= 32, m <= 32: the same algorithm with 32-wide LDS tiles; beyond: TFMPC_ERR_UNSUPPORTED.  B == 0 is a no-op. */
+const char *tfmpc_lqr_steady_state_kernel_name(int n, int m);
+int tfmpc_lqr_steady_state_f32(int B, int n, int m,
+                               const float *F, long sF_b, const float *f, long sf_b,
+                               const float *C, long sC_b, const float *c, long sc_b,
+                               int max_iter, float tol,
+                               float *K, float *k, float *P, float *p,
+                               int32_t *iterations, int32_t *status, void *stream);
 
 /* --------------------------------------------------------------- iLQR --------
  * Control-limited iLQR (tfmpc/solvers/ilqr.py) over the reference's differentiable

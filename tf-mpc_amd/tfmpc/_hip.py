@@ -18,6 +18,7 @@ ERRORS = {-1: "bad argument", -2: "shape not supported by any kernel variant",
           -3: "kernel launch failed", -4: "workspace too small"}
 
 ST_SINGULAR, ST_NOT_PD, ST_NAN, ST_QP_MAXITER, ST_MAX_ATTEMPTS, ST_QP_LATER_NOT_PD, ST_ENV_FLAG = 1, 2, 4, 8, 16, 32, 64
+ST_NOT_STABILISING = 128      # tfmpc_lqr_steady_state_f32: no stabilising solution found
 
 _P, _I, _L, _Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t
 
@@ -52,6 +53,10 @@ _SIGNATURES.update({
     "tfmpc_tvlqr_vjp_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     # states actions, g_states g_actions g_costs, dF df dC dc (+ batch, time strides), dCfin dcfin dx0 (+ batch stride)
     "tfmpc_tvlqr_vjp_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3 + [_P, _P, _Z, _P]),
+    "tfmpc_lqr_steady_state_kernel_name": (ctypes.c_char_p, [_I, _I]),
+    # B n m, F f C c (+ batch strides), max_iter tol, K k P p, iterations status stream
+    "tfmpc_lqr_steady_state_f32": (_I, [_I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _I, ctypes.c_float,
+                                        _P, _P, _P, _P, _P, _P, _P]),
 })
 
 

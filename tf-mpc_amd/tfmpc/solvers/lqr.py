@@ -49,6 +49,24 @@ class ValueFn(list):
         self.V, self.v, self.const = V, v, const
 
 
+class SteadyState:
+    """The infinite-horizon solution of an :class:`LQR` (``LQR.steady_state``): the stationary feedback ``u = K x + k``
+    and value function ``V(x) = 1/2 x^T P x + p^T x`` as device tensors ``K[(B,)m,n]``, ``k[(B,)m,1]``, ``P[(B,)n,n]``,
+    ``p[(B,)n,1]``, with ``iterations[(B)]`` (doubling steps) and ``status[(B)]`` (``_hip.ST_*`` bits; a flagged instance
+    has NaN outputs)."""
+
+    def __init__(self, K, k, P, p, iterations, status):
+        self.K, self.k, self.P, self.p = K, k, P, p
+        self.iterations, self.status = iterations, status
+
+    def policy(self, T):
+        """The stationary controller as a :class:`Policy` of ``T`` steps: views of ``K``, ``k`` expanded along a time axis."""
+        T = int(T)
+        tdim = self.K.dim() - 2
+        expand = lambda t: t.unsqueeze(tdim).expand(*t.shape[:tdim], T, *t.shape[tdim:])    # noqa: E731
+        return Policy(expand(self.K), expand(self.k))
+
+
 def _as_f32(a, device):
     if isinstance(a, torch.Tensor):
         return a.detach().to(device=device, dtype=torch.float32)
@@ -293,6 +311,51 @@ class LQR:
         if self._resolve_batch(x0g) is None:
             states, actions, costs = states[0], actions[0], costs[0]
         return states, actions, costs
+
+    # -- infinite horizon (tfmpc_lqr_steady_state_f32) --------------
+    def steady_state(self, max_iter=None, tol=None):
+        """The stationary solution of this problem: the limits of ``backward(T)``'s ``K_0, k_0, V_0, v_0`` as T grows,
+        found by the structure-preserving doubling algorithm in one kernel launch.  ``max_iter`` caps the doubling steps
+        (default 40), ``tol`` is the relative change of P at which it stops (default 4 fp32 ulps).  Returns a
+        :class:`SteadyState`; never synchronises; sets ``last_status``.  An instance without a stabilising solution has
+        ``_hip.ST_NOT_STABILISING`` in its status and NaN outputs."""
+        if not self.symmetric_cost:
+            raise NotImplementedError("the steady state is served for a symmetric C only")
+        if tvlqr_grad.wants_grad(*self._sources):
+            raise NotImplementedError("gradients through the steady state are not served: call it under torch.no_grad() "
+                                      "or with operands that do not require grad")
+        if max_iter is None:
+            max_iter = 0
+        elif int(max_iter) != max_iter or int(max_iter) < 1:
+            raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
+        if tol is None:
+            tol = 0.0
+        elif not (np.isfinite(tol) and tol > 0):
+            raise ValueError(f"tol must be a positive finite number, got {tol!r}")
+        n, m = self.state_size, self.action_size
+        if n > 32 or m > 32:
+            raise ValueError(f"the steady-state kernels serve n <= 32 and m <= 32, got n={n}, m={m}")
+        lib = _hip.require_gpu()
+        B = self.batch_size
+        Bk = B if B is not None else 1
+        dev = self.device
+        K = torch.empty((Bk, m, n), device=dev)
+        k = torch.empty((Bk, m, 1), device=dev)
+        P = torch.empty((Bk, n, n), device=dev)
+        p = torch.empty((Bk, n, 1), device=dev)
+        iterations = torch.zeros((Bk,), dtype=torch.int32, device=dev)
+        status = torch.zeros((Bk,), dtype=torch.int32, device=dev)
+        args = []
+        for t in (self.F, self.f, self.C, self.c):        # (batch strides from the layout: an empty batch has no t[0])
+            args += [_hip.ptr(t), t.stride(0) if t.dim() == 3 else 0]
+        rc = lib.tfmpc_lqr_steady_state_f32(Bk, n, m, *args, int(max_iter), float(tol),
+                                            _hip.ptr(K), _hip.ptr(k), _hip.ptr(P), _hip.ptr(p),
+                                            _hip.ptr(iterations), _hip.ptr(status), _hip.stream())
+        _hip.check(rc, "tfmpc_lqr_steady_state_f32")
+        self.last_status = status
+        if B is None:
+            K, k, P, p, iterations, status = K[0], k[0], P[0], p[0], iterations[0], status[0]
+        return SteadyState(K, k, P, p, iterations, status)
 
     # -- lqr.py:168-181 ------------------------------------------------------------
     def dump(self, file):

@@ -96,13 +96,21 @@ class TimeVaryingLQR:
         return t.contiguous()
 
     @classmethod
-    def from_lqr(cls, lqr, T):
-        """The time-invariant problem of ``lqr`` over ``T`` steps as a TV problem: views with time stride 0."""
+    def from_lqr(cls, lqr, T, C_final=None, c_final=None):
+        """The time-invariant problem of ``lqr`` over ``T`` steps as a TV problem: views with time stride 0.  ``C_final``,
+        ``c_final`` replace the default final cost, e.g. ``from_lqr(lqr, T, ss.P, ss.p)`` with ``ss = lqr.steady_state()``:
+        the stationary value function as terminal cost of a short horizon.  ``C_final`` must be symmetric."""
         T = int(T)
         views = [t.unsqueeze(-3).expand(*t.shape[:-2], T, *t.shape[-2:]) for t in (lqr.F, lqr.f, lqr.C, lqr.c)]
         if not lqr.symmetric_cost:
             raise ValueError("only a symmetric C has a time-varying counterpart")
-        return cls(*views, device=lqr.device, symmetric=True)
+        if C_final is None and c_final is None:
+            return cls(*views, device=lqr.device, symmetric=True)
+        if C_final is None or c_final is None:
+            raise ValueError("give both C_final and c_final, or neither")
+        # C is known symmetric; C_final is checked here, NaN entries (a flagged steady-state instance) left out of the test
+        symmetric = _is_symmetric(torch.nan_to_num(_as_f32(C_final, lqr.device), nan=0.0))
+        return cls(*views, C_final, c_final, device=lqr.device, symmetric=symmetric)
 
     # -- properties ----------------------------------------------------------------
     @property

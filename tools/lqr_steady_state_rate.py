@@ -1,0 +1,142 @@
+"""Device-event times of the infinite-horizon LQR (tfmpc_lqr_steady_state_f32) at B = 65 536, n = 16, m = 8:
+
+  (a) make_lqr(16, 8) draws;
+  (b) the lightly damped workload (A orthogonal, B = 0.05 N(0, 1), C = diag(1e-3 I, I): closed-loop radius ~0.997);
+  (c) for scale, LQR.backward(T) on the same problems at the horizon T at which K_0 first matches the gain accuracy
+      of (a) / (b) (found in fp64 on sampled instances).  Its outputs grow with T, so at the long horizon it runs on
+      B / 8 instances and the time is scaled by 8 (reported as such);
+  (d) scipy.linalg.solve_discrete_are plus the gains on one CPU core, per instance.
+
+Instances are a pool of 512 distinct draws, instance b holding its own copy of pool[b % 512].  Prints one JSON object
+(median / min of --reps timed launches after --warmup).
+Usage: python tools/lqr_steady_state_rate.py [--reps 20] [--warmup 3] [--out file.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tf-mpc_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import lqr_steady_state_ref as ssref  # noqa: E402
+from tfmpc import _hip  # noqa: E402
+from tfmpc.solvers.lqr import LQR  # noqa: E402
+
+B, N, M, POOL = 65536, 16, 8, 512
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), float(np.min(ts))
+
+
+def gain_error(K, ref):
+    return float(np.abs(K - ref).max() / max(1.0, np.abs(ref).max()))
+
+
+def horizon_matching(F, f, C, c, target, cap=20000):
+    """Smallest T at which the fp64 finite recursion's K_0 is within `target` (relative) of the stationary gain."""
+    n = F.shape[0]
+    F, C = F.astype(np.float64), C.astype(np.float64)
+    Kss = ssref.steady_state(F, f, C, c)["K"]
+    V = C[:n, :n]
+    for T in range(1, cap + 1):
+        Q = C + F.T @ V @ F
+        K = -np.linalg.solve(Q[n:, n:], Q[n:, :n])
+        V = Q[:n, :n] + Q[:n, n:] @ K
+        V = 0.5 * (V + V.T)
+        if gain_error(K, Kss) <= target:
+            return T
+    return cap
+
+
+def line(name, pool, reps, warmup, sample=16):
+    F, f, C, c = pool
+    idx = np.arange(B) % POOL
+    lqr = LQR(F[idx], f[idx], C[idx], c[idx], device="cuda", symmetric=True)
+    ss = lqr.steady_state()
+    torch.cuda.synchronize()
+    status = ss.status.cpu().numpy()
+    its = ss.iterations.cpu().numpy()
+    K = ss.K.cpu().numpy()
+    med, mn = timed(lambda: lqr.steady_state(), reps, warmup)
+    errs, horizons = [], []
+    for b in range(sample):
+        ref = ssref.steady_state(F[b], f[b], C[b], c[b])["K"]
+        errs.append(gain_error(K[b], ref))
+    target = float(np.median(errs))
+    for b in range(sample):
+        horizons.append(horizon_matching(F[b], f[b], C[b], c[b], target))
+    T = int(np.median(horizons))
+    scale = 1 if T <= 100 else 8
+    sub = LQR(F[idx[:B // scale]], f[idx[:B // scale]], C[idx[:B // scale]], c[idx[:B // scale]], device="cuda", symmetric=True)
+    bmed, bmin = timed(lambda: sub.backward(T), max(3, reps // 4) if scale > 1 else reps, 1 if scale > 1 else warmup)
+    return {
+        f"{name}_ms": med, f"{name}_min_ms": mn, f"{name}_flagged": int((status != 0).sum()),
+        f"{name}_iterations_median": float(np.median(its)), f"{name}_iterations_max": int(its.max()),
+        f"{name}_gain_rel_error_median": target,
+        f"{name}_backward_T": T, f"{name}_backward_batch": B // scale,
+        f"{name}_backward_ms": bmed * scale, f"{name}_backward_min_ms": bmin * scale,
+        f"{name}_speedup_vs_backward": bmed * scale / med,
+    }
+
+
+def scipy_per_instance(pool, count=64):
+    import scipy.linalg
+    from threadpoolctl import threadpool_limits
+    F, f, C, c = (a.astype(np.float64) for a in pool)
+    n = N
+    with threadpool_limits(1):
+        return _scipy_loop(scipy.linalg, F, C, n, count)
+
+
+def _scipy_loop(linalg, F, C, n, count):
+    t0 = time.perf_counter()
+    for b in range(count):
+        A, Bm = F[b][:, :n], F[b][:, n:]
+        Q, S, R = C[b][:n, :n], C[b][:n, n:], C[b][n:, n:]
+        P = linalg.solve_discrete_are(A, Bm, Q, R, s=S)
+        np.linalg.solve(R + Bm.T @ P @ Bm, Bm.T @ P @ A + S.T)
+    return (time.perf_counter() - t0) / count * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    _hip.require_gpu()
+    torch.cuda.set_device(0)
+    a = ssref.make_lqr_batch(N, M, POOL, seed=0)
+    d = ssref.damped_workload(N, M, POOL, seed=0)
+    out = {"B": B, "n": N, "m": M, "kernel": _hip.load().tfmpc_lqr_steady_state_kernel_name(N, M).decode(), "reps": args.reps}
+    out.update(line("a_make_lqr", a, args.reps, args.warmup))
+    out.update(line("b_damped", d, args.reps, args.warmup))
+    out["d_scipy_ms_per_instance_make_lqr"] = scipy_per_instance(a)
+    out["d_scipy_ms_per_instance_damped"] = scipy_per_instance(d)
+    text = json.dumps(out)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
