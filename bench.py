@@ -12,7 +12,7 @@ backward sweep + closed-loop rollout of every instance of its shard); for an LQR
 one solve is one iLQR iteration.  Inputs are resident in HBM before the
 timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher (WORLD_SIZE unset) starts the N ranks itself: a
@@ -21,12 +21,16 @@ The headline batch is drawn by tests/problems.py:make_lqr_batch_spd -- the refer
 make_lqr (tfmpc/envs/__init__.py:9-18) vectorised: F, f, c ~ N(0,1), C by make_spd_matrix's
 formula (eigenvalues ~1e-3 .. n+m).
 
-Prints ONE JSON line on rank 0 (see the task contract) with `ms_per_step`, `roofline`
-for the dominant kernel and `cpu_baseline` (the oracle's C port timed on this host).
-The line stays a few KB: the full secondary measurements go to bench_extra.json beside
-this file, their compact `extra_summary` into the line.  `--dump-outputs DIR` writes
-what the last timed step returned (states, actions, costs, status; a fixed sample of
-instances within 64 MB) as DIR/<name>.npy, float32, for comparing two builds.
+Prints ONE JSON line on rank 0 (see the task contract) with `ms_per_step` and the
+`roofline` of the dominant kernel over the timed steps.  A plain run does only what that
+line needs: set-up (with the untimed launches that precede the warm-up, see main()),
+warm-up, the timed steps, --dump-outputs, the line.  `--full` adds every other
+measurement: the strict-f32 variant of the kernel, `cpu_baseline` (the oracle's C port
+timed on this host) and the secondary workloads, whose full blocks go to bench_extra.json
+beside this file and their compact `extra_summary` into the line (which stays a few KB).
+`--dump-outputs DIR` writes what the last timed step returned (states, actions, costs,
+status; a fixed sample of instances within 64 MB) as DIR/<name>.npy, float32, for
+comparing two builds.
 """
 
 import argparse
@@ -972,8 +976,12 @@ def main():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong (default; BASELINE configs[2]: batch=65 536 sharded over 1->8 GPUs): --batch is the global batch, "
                          "block-sharded over the ranks; weak: --batch instances on every GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary iLQR-API measurement (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need: the strict-f32 variant of the kernel, the CPU "
+                         "baseline and the secondary workloads (`extra`, bench_extra.json); a run without it is set-up, warm-up, "
+                         "the timed steps, --dump-outputs and the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads (`extra`)")
     ap.add_argument("--extras-only", action="store_true",
                     help="internal: the child process of a single-GPU run that measures the secondary numbers (`extra`); "
                          "it waits for a line on stdin before it touches the GPU and prints one JSON object")
@@ -1011,7 +1019,7 @@ def main():
     # The secondary numbers (`extra`) run in a CHILD process, started here -- before this process touches the GPU (no
     # exec after GPU initialisation) -- and idle until the headline measurement is over: whatever happens in one of the
     # secondary kernels, the headline line is printed.
-    extras_child = spawn_extras(args) if (world == 1 and not use_dist and not args.no_extra) else None
+    extras_child = spawn_extras(args) if (args.full and world == 1 and not use_dist and not args.no_extra) else None
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
     torch.cuda.set_device(local_rank)
@@ -1053,9 +1061,11 @@ def main():
         torch.cuda.synchronize()
 
     # the same steps with the sweep's products on the f32 matrix-core instruction (TFMPC_LQR_MFMA=f32): the strict
-    # variant of the kernel, reported beside the default (bf16x3) -- not part of `value`.  Measured BEFORE the warm-up
-    # and the timed steps: a process's first ~40 launches run 5-8 % slower than its steady state (1.92 -> 1.78 ms on one
-    # box, tools/probes/stream_effect_headline.py), so what has to run anyway runs first.
+    # variant of the kernel, reported beside the default (bf16x3) with --full -- not part of `value`.  Measured BEFORE
+    # the warm-up and the timed steps: a process's first ~40 launches run 5-8 % slower than its steady state (1.92 -> 1.78
+    # ms on one box, tools/probes/stream_effect_headline.py), so what has to run anyway runs first.  A plain run makes the
+    # same launches and leaves them unreported: they are part of what precedes the timed steps, and without them those
+    # steps ran 4 % slower at --steps 20 --warmup 3 and 16 % slower at --steps 5 --warmup 1.
     f32_ms, f32_launches = None, 0
     lqr_mfma_override = _hip.get_option("TFMPC_LQR_MFMA")     # an A/B run may have exported a variant: then the headline IS that variant
     if world == 1 and not use_dist and lqr_mfma_override is None:
@@ -1068,7 +1078,8 @@ def main():
                 step()
             e1.record()
             torch.cuda.synchronize()
-        f32_ms = e0.elapsed_time(e1) / max(1, args.steps // 2)
+        if args.full:
+            f32_ms = e0.elapsed_time(e1) / max(1, args.steps // 2)
         f32_launches = 3 + max(1, args.steps // 2)
 
     for _ in range(args.warmup):
@@ -1185,7 +1196,7 @@ def main():
                               if world == 1 else None}
         if gather_error is not None:
             line["gather_error"] = gather_error
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(n, m, T)
             except Exception as exc:                          # noqa: BLE001 -- a secondary number must never cost the headline line
@@ -1203,13 +1214,14 @@ def main():
             except OSError as exc:
                 line["extra_file_error"] = repr(exc)
             line["extra_summary"] = summarise_extras(extra)
-        # five keys FIRST in the line (a log that keeps only the head of the line still shows them), the full blocks follow
-        sx = line.get("extra_summary") or {}
-        first = {"summary": {"headline_frac_of_fp32_peak": round(achieved / PEAK_F32_TFLOPS, 4),
-                             "strict_f32_variant_frac": None if f32_ms is None else round(line["strict_f32_variant"]["frac"], 4),
-                             "lqr_mfma_option": line["lqr_mfma_option"],
-                             "ilqr_api_warm_ms_frac": sx.get("ilqr_api_warm"),
-                             "secondary_ms_frac": {k: sx.get(k) for k in ("cfg5_hvac", "cfg5_reservoir", "hvac6", "res4", "literal_dims") if k in sx}}}
+        # the summary FIRST in the line (a log that keeps only the head of the line still shows it), the full blocks follow
+        summary = {"headline_frac_of_fp32_peak": round(achieved / PEAK_F32_TFLOPS, 4), "lqr_mfma_option": line["lqr_mfma_option"]}
+        if args.full:
+            sx = line.get("extra_summary") or {}
+            summary.update(strict_f32_variant_frac=None if f32_ms is None else round(line["strict_f32_variant"]["frac"], 4),
+                           ilqr_api_warm_ms_frac=sx.get("ilqr_api_warm"),
+                           secondary_ms_frac={k: sx.get(k) for k in ("cfg5_hvac", "cfg5_reservoir", "hvac6", "res4", "literal_dims") if k in sx})
+        first = {"summary": summary}
         first.update(line)
         print(json.dumps(_finite(first), allow_nan=False), flush=True)
 
