@@ -263,6 +263,30 @@ int tfmpc_lqr_steady_state_f32(int B, int n, int m,
                                float *K, float *k, float *P, float *p,
                                int32_t *iterations, int32_t *status, void *stream);
 
+/* Vector-Jacobian product of tfmpc_lqr_steady_state_f32: given the forward's K[B][m][n], k[B][m],
+ * P[B][n][n], p[B][n] and status[B] (fwd_status), and upstream gradients gK, gk, gP, gp of the same per-instance layout
+ * (each NULL = zero), writes the gradients of <gK, K> + <gk, k> + <gP, P> + <gp, p> with respect to F, f, C, c.  Model
+ * operands and their batch strides as in the forward.  The explicit formulas of K, k, p are reversed with one
+ * elimination of R + B'PB (without pivoting: TFMPC_ST_NOT_PD) and one of I - A_cl (pivoted: TFMPC_ST_SINGULAR); P's
+ * dependence through the Riccati equation is one Stein solve Y = A_cl Y A_cl' + sym(Pbar) by Smith doubling, stopped
+ * when max|Phi Y Phi'| <= tol max|Y| and max|Phi^2| <= 1e-3 (max_iter = 0 / tol = 0.0f: 40 steps, 4 FLT_EPSILON),
+ * else TFMPC_ST_NOT_STABILISING.  Outputs dF[B][n][n+m], df[B][n], dC[B][d][d] (the symmetric gradient), dc[B][d], each
+ * with its own batch stride in elements; a NULL output is not computed, a stride of 0 SUMS the gradient over the batch
+ * (fixed-order reduction without atomics: repeated calls give identical bits).  status[B] (required) gets the forward's
+ * status where it was flagged, else the backward's; a flagged instance has NaN in its own gradient rows and in every
+ * batch-summed gradient.  workspace: tfmpc_lqr_steady_state_vjp_workspace_bytes(B, n, m) bytes serve any choice of
+ * summed outputs (NULL is fine when no output is summed).  Shapes as the forward serves; B == 0 is a no-op. */
+size_t tfmpc_lqr_steady_state_vjp_workspace_bytes(int B, int n, int m);
+const char *tfmpc_lqr_steady_state_vjp_kernel_name(int n, int m);
+int tfmpc_lqr_steady_state_vjp_f32(int B, int n, int m,
+                                   const float *F, long sF_b, const float *f, long sf_b,
+                                   const float *C, long sC_b, const float *c, long sc_b,
+                                   const float *K, const float *k, const float *P, const float *p, const int32_t *fwd_status,
+                                   const float *gK, const float *gk, const float *gP, const float *gp,
+                                   int max_iter, float tol,
+                                   float *dF, long sdF_b, float *df, long sdf_b, float *dC, long sdC_b, float *dc, long sdc_b,
+                                   int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* --------------------------------------------------------------- iLQR --------
  * Control-limited iLQR (tfmpc/solvers/ilqr.py) over the reference's differentiable
  * environments (tfmpc/envs).  An environment is described by a kind tag plus

@@ -1,0 +1,431 @@
+// lqr_steady_state_vjp.hip -- gradients of the infinite-horizon LQR (tfmpc_lqr_steady_state_vjp_f32, include/tfmpc_hip.h;
+// DESIGN.md 3.10).
+//
+// Given the forward's K, k, P, p (tfmpc_lqr_steady_state_f32) and upstream gradients gK, gk, gP, gp, one wavefront per
+// instance reverses the explicit formulas and then P's implicit dependence through the Riccati equation:
+//   G = R + B'PB, A_cl = A + BK (recomputed from the saved K, P), w = Pf + p
+//   [G^-1 | kappa] = G^-1 [I | gk]                       (elimination without pivoting: a non-positive pivot is NOT_PD)
+//   wbar = -B kappa,  rho = (I - A_cl)^-1 (gp + wbar)    (pivoted elimination: a zero pivot is SINGULAR)
+//   v = wbar + A_cl rho,  df = P v,  dc = [rho; K rho - kappa]
+//   Kbar = gK + (c_u + B'w) rho',  L = -G^-1 Kbar,  Gbar = -kappa k' + L K'
+//   Pbar = gP + v f' + B ([L | Gbar] F')
+//   Y = A_cl Y A_cl' + sym(Pbar)                         (Smith doubling: Y += sym(Phi Y Phi'), Phi <- Phi^2, Phi_0 = A_cl)
+//   dA = w rho' + [PB | P A_cl] [L; 2Y],  dB = w (K rho - kappa)' + [PA | PB | P A_cl] [L'; Gbar + Gbar'; 2 Y K']
+//   dC = sym([[Y, L' + 2 Y K'], [0, Gbar + K Y K']])
+// The Smith loop stops when max|Phi Y Phi'| <= tol max|Y| and max|Phi^2| <= kPhiZero, within max_iter steps; otherwise,
+// or on a non-finite value, the instance is NOT_STABILISING.  A flagged instance (forward or backward) gets NaN in its
+// own gradient rows.
+//
+// Layout as the forward (lqr_steady_state.hip): NP = 16 serves n, m <= 16, NP = 32 serves n, m <= 32, every matrix in
+// the wave's LDS slice, every product on v_mfma_f32_16x16x4_f32 (wave_ops.h mfma_matmul, strict fp32).  A gradient
+// whose batch stride is 0 is summed over the batch: the instance kernel writes per-instance records into the workspace,
+// then ss_vjp_reduce_stage1 (fixed-order sums over chunks of instances) and ss_vjp_reduce_stage2 (fixed-order sum of
+// the chunks) write the output.  No atomics: the same call gives the same bits.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cstdint>
+
+#include "../../include/tfmpc_hip.h"
+#include "wave_ops.h"
+
+namespace tfmpc {
+
+namespace {
+
+constexpr int kVjpMaxIter = 40;
+constexpr float kVjpTol = 4.0f * FLT_EPSILON;
+constexpr float kPhiZero = 1e-3f;
+constexpr int kRedChunk = 64;          // instances per stage-1 block
+constexpr int kRedThreads = 256;
+enum { kOutF, kOutf, kOutC, kOutc, kOuts };
+
+struct VjpOut {
+    float *p;
+    long sb;          // batch stride in elements (a workspace record when the caller's stride is 0)
+};
+
+struct SsVjpArgs {
+    int B, n, m, max_iter;
+    float tol;
+    const float *F, *f, *C, *c;
+    long sF, sf, sC, sc;
+    const float *K, *k, *P, *p;
+    const int32_t *fwd_status;
+    const float *gK, *gk, *gP, *gp;
+    VjpOut o[kOuts];
+    int32_t *status;
+};
+
+__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= FLT_MAX; }
+
+template <int NP>
+__global__ __launch_bounds__(kWave) void ss_vjp_kernel(SsVjpArgs a)
+{
+    constexpr int LDN = NP + 1, LDD = 2 * NP + 1;
+    __shared__ float sF[NP * LDD], aug[NP * LDD];
+    __shared__ float sK[NP * LDN], sP[NP * LDN], sAcl[NP * LDN], sPB[NP * LDN], sL[NP * LDN], sGb[NP * LDN];
+    __shared__ float sY[NP * LDN], sT1[NP * LDN], sT2[NP * LDN], sT3[NP * LDN];
+    __shared__ float vf[NP], vc[2 * NP], vk[NP], vp[NP], vw[NP], vwbar[NP], vrho[NP], vKrho[NP], vv[NP], vy[NP];
+    __shared__ float vkap[NP], fac[NP];
+
+    const int b = blockIdx.x;
+    const int lane = lane_id();
+    const int n = a.n, m = a.m, d = n + m;
+    int status = a.fwd_status[b];
+    int it = 0;
+    const float *Cg = a.C + (size_t)b * a.sC;
+    auto Am = [&](int i, int j) { return sF[i * LDD + j]; };           // A[n][n]
+    auto Bm = [&](int i, int j) { return sF[i * LDD + n + j]; };       // B[n][m]
+    auto zero = [](int, int) { return 0.0f; };
+
+    if (!status) {
+        load_matrix(sF, LDD, a.F + (size_t)b * a.sF, n, d);
+        load_matrix(sK, LDN, a.K + (size_t)b * m * n, m, n);
+        load_matrix(sP, LDN, a.P + (size_t)b * n * n, n, n);
+        for (int i = lane; i < n; i += kWave) {
+            vf[i] = a.f[(size_t)b * a.sf + i];
+            vp[i] = a.p[(size_t)b * n + i];
+        }
+        for (int i = lane; i < d; i += kWave) vc[i] = a.c[(size_t)b * a.sc + i];
+        for (int i = lane; i < m; i += kWave) vk[i] = a.k[(size_t)b * m + i];
+        wsync();
+        // PB = P B [n][m], A_cl = A + B K, w = P f + p
+        wave_matmul_mfma(n, m, n, [&](int i, int kk) { return sP[i * LDN + kk]; }, Bm, zero,
+                         [&](int i, int j, float x) { sPB[i * LDN + j] = x; });
+        wave_matmul_mfma(n, n, m, Bm, [&](int kk, int j) { return sK[kk * LDN + j]; }, Am,
+                         [&](int i, int j, float x) { sAcl[i * LDN + j] = x; });
+        for (int i = lane; i < n; i += kWave) {
+            float s = 0.0f;
+            for (int j = 0; j < n; ++j) s = fmaf(sP[i * LDN + j], vf[j], s);
+            vw[i] = s + vp[i];
+        }
+        wsync();
+        // aug = [R + B'PB | I | gk]  (m rows), R + B'PB symmetrised as in the forward
+        wave_matmul_mfma(m, m, n, [&](int i, int kk) { return Bm(kk, i); }, [&](int kk, int j) { return sPB[kk * LDN + j]; },
+                         [&](int i, int j) { return Cg[(n + i) * d + n + j]; }, [&](int i, int j, float x) { aug[i * LDD + j] = x; });
+        wave_for_2d(m, m + 1, [&](int r, int j, int) {
+            aug[r * LDD + m + j] = j < m ? (r == j ? 1.0f : 0.0f) : (a.gk ? a.gk[(size_t)b * m + r] : 0.0f);
+        });
+        wsync();
+        wave_for_2d(m, m, [&](int i, int j, int) {
+            if (i < j) {
+                const float s = 0.5f * (aug[i * LDD + j] + aug[j * LDD + i]);
+                aug[i * LDD + j] = s;
+                aug[j * LDD + i] = s;
+            }
+        });
+        wsync();
+        if (wave_gauss_jordan<false>(aug, LDD, m, 2 * m + 1, fac, fac)) status |= TFMPC_ST_NOT_PD;
+    }
+    auto Gi = [&](int i, int j) { return aug[i * LDD + m + j]; };       // G^-1 [m][m]
+
+    if (!status) {
+        for (int r = lane; r < m; r += kWave) vkap[r] = aug[r * LDD + 2 * m];
+        wsync();
+        // wbar = -B kappa;  T1 = [I - A_cl | gp + wbar]  (n rows)
+        for (int i = lane; i < n; i += kWave) {
+            float s = 0.0f;
+            for (int r = 0; r < m; ++r) s = fmaf(Bm(i, r), vkap[r], s);
+            vwbar[i] = -s;
+            sT1[i * LDN + n] = (a.gp ? a.gp[(size_t)b * n + i] : 0.0f) - s;
+        }
+        wave_for_2d(n, n, [&](int i, int j, int) { sT1[i * LDN + j] = (i == j ? 1.0f : 0.0f) - sAcl[i * LDN + j]; });
+        wsync();
+        if (wave_gauss_jordan<true>(sT1, LDN, n, n + 1, fac, fac)) status |= TFMPC_ST_SINGULAR;
+    }
+
+    if (!status) {
+        for (int i = lane; i < n; i += kWave) vrho[i] = sT1[i * LDN + n];
+        wsync();
+        // K rho, v = wbar + A_cl rho, y = c_u + B'w
+        for (int r = lane; r < m; r += kWave) {
+            float s1 = 0.0f, s2 = 0.0f;
+            for (int j = 0; j < n; ++j) {
+                s1 = fmaf(sK[r * LDN + j], vrho[j], s1);
+                s2 = fmaf(Bm(j, r), vw[j], s2);
+            }
+            vKrho[r] = s1;
+            vy[r] = vc[n + r] + s2;
+        }
+        for (int i = lane; i < n; i += kWave) {
+            float s = 0.0f;
+            for (int j = 0; j < n; ++j) s = fmaf(sAcl[i * LDN + j], vrho[j], s);
+            vv[i] = vwbar[i] + s;
+        }
+        wsync();
+        // T2 = Kbar = gK + y rho'  [m][n]
+        wave_for_2d(m, n, [&](int i, int j, int idx) {
+            sT2[i * LDN + j] = fmaf(vy[i], vrho[j], a.gK ? a.gK[(size_t)b * m * n + idx] : 0.0f);
+        });
+        wsync();
+        // L = -G^-1 Kbar [m][n]
+        wave_matmul_mfma(m, n, m, [&](int i, int kk) { return -Gi(i, kk); }, [&](int kk, int j) { return sT2[kk * LDN + j]; }, zero,
+                         [&](int i, int j, float x) { sL[i * LDN + j] = x; });
+        wsync();
+        // Gbar = -kappa k' + L K' [m][m]
+        wave_matmul_mfma(m, m, n, [&](int i, int kk) { return sL[i * LDN + kk]; }, [&](int kk, int j) { return sK[j * LDN + kk]; },
+                         [&](int i, int j) { return -(vkap[i] * vk[j]); }, [&](int i, int j, float x) { sGb[i * LDN + j] = x; });
+        wsync();
+        // T2 = U = [L | Gbar] F'  [m][n]
+        wave_matmul_mfma(m, n, d, [&](int i, int kk) { return kk < n ? sL[i * LDN + kk] : sGb[i * LDN + kk - n]; },
+                         [&](int kk, int j) { return sF[j * LDD + kk]; }, zero, [&](int i, int j, float x) { sT2[i * LDN + j] = x; });
+        wsync();
+        // T1 = Pbar = gP + v f' + B U  [n][n]
+        wave_matmul_mfma(n, n, m, Bm, [&](int kk, int j) { return sT2[kk * LDN + j]; },
+                         [&](int i, int j) { return fmaf(vv[i], vf[j], a.gP ? a.gP[(size_t)b * n * n + i * n + j] : 0.0f); },
+                         [&](int i, int j, float x) { sT1[i * LDN + j] = x; });
+        wsync();
+        wave_for_2d(n, n, [&](int i, int j, int) { sY[i * LDN + j] = 0.5f * (sT1[i * LDN + j] + sT1[j * LDN + i]); });
+        wsync();
+
+        // Smith doubling on Y = A_cl Y A_cl' + sym(Pbar): Phi ping-pongs between A_cl's tile and T3
+        float *phi = sAcl, *phi2 = sT3;
+        bool converged = false;
+        while (it < a.max_iter) {
+            ++it;
+            wave_matmul_mfma(n, n, n, [&](int i, int kk) { return phi[i * LDN + kk]; }, [&](int kk, int j) { return sY[kk * LDN + j]; },
+                             zero, [&](int i, int j, float x) { sT2[i * LDN + j] = x; });          // T2 = Phi Y
+            wsync();
+            float pmax = 0.0f;
+            bool bad = false;          // (fmaxf drops a NaN operand: non-finite entries are counted on their own)
+            wave_matmul_mfma(n, n, n, [&](int i, int kk) { return sT2[i * LDN + kk]; }, [&](int kk, int j) { return phi[j * LDN + kk]; },
+                             zero, [&](int i, int j, float x) { sT1[i * LDN + j] = x; });          // T1 = Phi Y Phi'
+            wave_matmul_mfma(n, n, n, [&](int i, int kk) { return phi[i * LDN + kk]; }, [&](int kk, int j) { return phi[kk * LDN + j]; },
+                             zero, [&](int i, int j, float x) {
+                                 phi2[i * LDN + j] = x;
+                                 bad |= !finite(x);
+                                 pmax = fmaxf(pmax, fabsf(x));
+                             });                                                                    // Phi^2
+            wsync();
+            float dmax = 0.0f, ymax = 0.0f;
+            wave_for_2d(n, n, [&](int i, int j, int) {
+                const float x = sT1[i * LDN + j];
+                const float y = sY[i * LDN + j] + 0.5f * (x + sT1[j * LDN + i]);
+                sY[i * LDN + j] = y;
+                bad |= !(finite(x) && finite(y));
+                dmax = fmaxf(dmax, fabsf(x));
+                ymax = fmaxf(ymax, fabsf(y));
+            });
+            const bool nonfinite = __ballot(bad) != 0;
+            dmax = wave_max(dmax);
+            ymax = wave_max(ymax);
+            pmax = wave_max(pmax);
+            float *t = phi;
+            phi = phi2;
+            phi2 = t;
+            wsync();
+            if (nonfinite) break;
+            if (dmax <= a.tol * ymax && pmax <= kPhiZero) {
+                converged = true;
+                break;
+            }
+        }
+        if (!converged) status |= TFMPC_ST_NOT_STABILISING;
+    }
+
+    const bool ok = status == 0;
+    if (ok) {
+        // T1 = K Y [m][n], T2 = P A [n][n]; then Acl's tile = W = P A_cl = PA + PB K, T3 = Rbar = Gbar + (KY) K' [m][m]
+        wave_matmul_mfma(m, n, n, [&](int i, int kk) { return sK[i * LDN + kk]; }, [&](int kk, int j) { return sY[kk * LDN + j]; }, zero,
+                         [&](int i, int j, float x) { sT1[i * LDN + j] = x; });
+        wave_matmul_mfma(n, n, n, [&](int i, int kk) { return sP[i * LDN + kk]; }, Am, zero,
+                         [&](int i, int j, float x) { sT2[i * LDN + j] = x; });
+        wsync();
+        wave_matmul_mfma(n, n, m, [&](int i, int kk) { return sPB[i * LDN + kk]; }, [&](int kk, int j) { return sK[kk * LDN + j]; },
+                         [&](int i, int j) { return sT2[i * LDN + j]; }, [&](int i, int j, float x) { sAcl[i * LDN + j] = x; });
+        wave_matmul_mfma(m, m, n, [&](int i, int kk) { return sT1[i * LDN + kk]; }, [&](int kk, int j) { return sK[j * LDN + kk]; },
+                         [&](int i, int j) { return sGb[i * LDN + j]; }, [&](int i, int j, float x) { sT3[i * LDN + j] = x; });
+        wsync();
+        const VjpOut &oF = a.o[kOutF], &of = a.o[kOutf], &oC = a.o[kOutC], &oc = a.o[kOutc];
+        if (oF.p) {
+            float *dF = oF.p + (size_t)b * oF.sb;
+            // dA = w rho' + [PB | W] [L; 2Y]
+            wave_matmul_mfma(n, n, m + n, [&](int i, int kk) { return kk < m ? sPB[i * LDN + kk] : sAcl[i * LDN + kk - m]; },
+                             [&](int kk, int j) { return kk < m ? sL[kk * LDN + j] : 2.0f * sY[(kk - m) * LDN + j]; },
+                             [&](int i, int j) { return vw[i] * vrho[j]; }, [&](int i, int j, float x) { dF[i * d + j] = x; });
+            // dB = w (K rho - kappa)' + [PA | PB | W] [L'; Gbar + Gbar'; 2 (KY)']
+            wave_matmul_mfma(n, m, 2 * n + m,
+                             [&](int i, int kk) {
+                                 return kk < n ? sT2[i * LDN + kk] : kk < n + m ? sPB[i * LDN + kk - n] : sAcl[i * LDN + kk - n - m];
+                             },
+                             [&](int kk, int j) {
+                                 return kk < n ? sL[j * LDN + kk]
+                                        : kk < n + m ? sGb[(kk - n) * LDN + j] + sGb[j * LDN + kk - n]
+                                                     : 2.0f * sT1[j * LDN + kk - n - m];
+                             },
+                             [&](int i, int j) { return vw[i] * (vKrho[j] - vkap[j]); }, [&](int i, int j, float x) { dF[i * d + n + j] = x; });
+        }
+        if (oC.p) {
+            float *dC = oC.p + (size_t)b * oC.sb;
+            auto Sbar = [&](int i, int j) { return sL[j * LDN + i] + 2.0f * sT1[j * LDN + i]; };      // L' + 2 (KY)' [n][m]
+            wave_for_2d(d, d, [&](int i, int j, int idx) {
+                float x;
+                if (i < n && j < n) x = 0.5f * (sY[i * LDN + j] + sY[j * LDN + i]);
+                else if (i < n) x = 0.5f * Sbar(i, j - n);
+                else if (j < n) x = 0.5f * Sbar(j, i - n);
+                else x = 0.5f * (sT3[(i - n) * LDN + j - n] + sT3[(j - n) * LDN + i - n]);
+                dC[idx] = x;
+            });
+        }
+        if (of.p) {
+            float *df = of.p + (size_t)b * of.sb;
+            for (int i = lane; i < n; i += kWave) {
+                float s = 0.0f;
+                for (int j = 0; j < n; ++j) s = fmaf(sP[i * LDN + j], vv[j], s);
+                df[i] = s;
+            }
+        }
+        if (oc.p) {
+            float *dc = oc.p + (size_t)b * oc.sb;
+            for (int i = lane; i < d; i += kWave) dc[i] = i < n ? vrho[i] : vKrho[i - n] - vkap[i - n];
+        }
+    } else {
+        const float qnan = __builtin_nanf("");
+        const int sizes[kOuts] = {n * d, n, d * d, d};
+        for (int k = 0; k < kOuts; ++k)
+            if (a.o[k].p)
+                for (int i = lane; i < sizes[k]; i += kWave) a.o[k].p[(size_t)b * a.o[k].sb + i] = qnan;
+    }
+    if (lane == 0) a.status[b] = status;
+}
+
+// partial[chunk][e] = sum of rec[b][e] over the chunk's instances, in a fixed order: four interleaved running sums
+// (instances b0 + 4i + q), then ((s0 + s1) + (s2 + s3)).  Grid (chunks, element slices of kRedThreads).
+__global__ void __launch_bounds__(kRedThreads) ss_vjp_reduce_stage1(const float *rec, int B, int nE, float *partial)
+{
+    const int chunk = blockIdx.x;
+    const int e = blockIdx.y * kRedThreads + threadIdx.x;
+    if (e >= nE) return;
+    const int b0 = chunk * kRedChunk, b1 = min(B, b0 + kRedChunk);
+    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int bb = b0;
+    for (; bb + 4 <= b1; bb += 4)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] += rec[(size_t)(bb + q) * nE + e];
+    for (int q = 0; bb < b1; ++bb, ++q) s[q] += rec[(size_t)bb * nE + e];
+    partial[(size_t)chunk * nE + e] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// out[e] = sum over the chunks of partial[chunk][e]: one block per element, strided partial sums per thread, then a
+// fixed-order tree over the block in LDS
+__global__ void __launch_bounds__(kRedThreads) ss_vjp_reduce_stage2(const float *partial, int chunks, int nE, float *out)
+{
+    __shared__ float t[kRedThreads];
+    const int e = blockIdx.x, tid = threadIdx.x;
+    float s = 0.0f;
+    for (int k = tid; k < chunks; k += kRedThreads) s += partial[(size_t)k * nE + e];
+    t[tid] = s;
+    __syncthreads();
+    for (int w = kRedThreads / 2; w > 0; w >>= 1) {
+        if (tid < w) t[tid] += t[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[e] = t[0];
+}
+
+bool fast_supported(int n, int m) { return n <= 16 && m <= 16; }
+
+size_t up64(size_t x) { return (x + 63) / 64 * 64; }
+
+int out_size(int k, int n, int m)
+{
+    const int d = n + m;
+    return k == kOutF ? n * d : k == kOutf ? n : k == kOutC ? d * d : d;
+}
+
+// workspace in floats: a record array [B][size] per summed output, then the stage-1 partial sums (reused by each output)
+size_t workspace_floats(int B, int n, int m, unsigned summed, size_t rec_off[kOuts], size_t *partial_off)
+{
+    const size_t chunks = ((size_t)B + kRedChunk - 1) / kRedChunk;
+    size_t o = 0, widest = 0;
+    for (int k = 0; k < kOuts; ++k) {
+        if (!(summed >> k & 1u)) continue;
+        if (rec_off) rec_off[k] = o;
+        o += up64((size_t)B * out_size(k, n, m));
+        widest = widest > (size_t)out_size(k, n, m) ? widest : (size_t)out_size(k, n, m);
+    }
+    if (!summed) return 0;
+    if (partial_off) *partial_off = o;
+    return o + up64(chunks * widest);
+}
+
+}  // namespace
+
+}  // namespace tfmpc
+
+using namespace tfmpc;
+
+extern "C" {
+
+size_t tfmpc_lqr_steady_state_vjp_workspace_bytes(int B, int n, int m)
+{
+    if (B <= 1 || n <= 0 || m <= 0 || n > 32 || m > 32) return 0;
+    return workspace_floats(B, n, m, (1u << kOuts) - 1, nullptr, nullptr) * sizeof(float);
+}
+
+const char *tfmpc_lqr_steady_state_vjp_kernel_name(int n, int m)
+{
+    if (n <= 0 || m <= 0) return "invalid";
+    if (fast_supported(n, m)) return n == 16 ? "ss_vjp_mfma_16" : "ss_vjp_mfma_16 (padded)";
+    if (n <= 32 && m <= 32) return "ss_vjp_wave_32";
+    return "unsupported";
+}
+
+int tfmpc_lqr_steady_state_vjp_f32(int B, int n, int m,
+                                   const float *F, long sF_b, const float *f, long sf_b, const float *C, long sC_b,
+                                   const float *c, long sc_b,
+                                   const float *K, const float *k, const float *P, const float *p, const int32_t *fwd_status,
+                                   const float *gK, const float *gk, const float *gP, const float *gp,
+                                   int max_iter, float tol,
+                                   float *dF, long sdF_b, float *df, long sdf_b, float *dC, long sdC_b, float *dc, long sdc_b,
+                                   int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (B < 0 || n <= 0 || m <= 0 || max_iter < 0 || !(tol >= 0.0f)) return TFMPC_ERR_ARG;
+    if (n > 32 || m > 32) return TFMPC_ERR_UNSUPPORTED;
+    if (B == 0) return TFMPC_OK;
+    if (!F || !f || !C || !c || !K || !k || !P || !p || !fwd_status || !status) return TFMPC_ERR_ARG;
+    for (long s : {sF_b, sf_b, sC_b, sc_b, sdF_b, sdf_b, sdC_b, sdc_b})
+        if (s < 0) return TFMPC_ERR_ARG;
+    float *outs[kOuts] = {dF, df, dC, dc};
+    const long strides[kOuts] = {sdF_b, sdf_b, sdC_b, sdc_b};
+    // a stride of 0 sums over the batch; over a batch of one the sum is the instance's own gradient, written in place
+    unsigned summed = 0;
+    for (int q = 0; q < kOuts; ++q)
+        if (outs[q] && strides[q] == 0 && B > 1) summed |= 1u << q;
+    size_t rec_off[kOuts] = {}, partial_off = 0;
+    const size_t need = workspace_floats(B, n, m, summed, rec_off, &partial_off);
+    if (need && (!workspace || workspace_bytes < need * sizeof(float))) return TFMPC_ERR_WORKSPACE;
+    float *w = static_cast<float *>(workspace);
+
+    SsVjpArgs a{};
+    a.B = B; a.n = n; a.m = m;
+    a.max_iter = max_iter ? max_iter : kVjpMaxIter;
+    a.tol = tol > 0.0f ? tol : kVjpTol;
+    a.F = F; a.f = f; a.C = C; a.c = c;
+    a.sF = sF_b; a.sf = sf_b; a.sC = sC_b; a.sc = sc_b;
+    a.K = K; a.k = k; a.P = P; a.p = p; a.fwd_status = fwd_status;
+    a.gK = gK; a.gk = gk; a.gP = gP; a.gp = gp;
+    for (int q = 0; q < kOuts; ++q) {
+        if (summed >> q & 1u) a.o[q] = {w + rec_off[q], (long)out_size(q, n, m)};
+        else a.o[q] = {outs[q], strides[q]};
+    }
+    a.status = status;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (fast_supported(n, m)) hipLaunchKernelGGL(ss_vjp_kernel<16>, dim3(B), dim3(kWave), 0, s, a);
+    else hipLaunchKernelGGL(ss_vjp_kernel<32>, dim3(B), dim3(kWave), 0, s, a);
+    if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
+    const int chunks = (B + kRedChunk - 1) / kRedChunk;
+    for (int q = 0; q < kOuts; ++q) {
+        if (!(summed >> q & 1u)) continue;
+        const int nE = out_size(q, n, m);
+        hipLaunchKernelGGL(ss_vjp_reduce_stage1, dim3(chunks, (nE + kRedThreads - 1) / kRedThreads), dim3(kRedThreads), 0, s,
+                           w + rec_off[q], B, nE, w + partial_off);
+        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
+        hipLaunchKernelGGL(ss_vjp_reduce_stage2, dim3(nE), dim3(kRedThreads), 0, s, w + partial_off, chunks, nE, outs[q]);
+        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
+    }
+    return TFMPC_OK;
+}
+
+}  // extern "C"

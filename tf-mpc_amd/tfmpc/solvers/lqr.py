@@ -313,17 +313,24 @@ class LQR:
         return states, actions, costs
 
     # -- infinite horizon (tfmpc_lqr_steady_state_f32) --------------
-    def steady_state(self, max_iter=None, tol=None):
+    def steady_state(self, max_iter=None, tol=None, differentiable=False):
         """The stationary solution of this problem: the limits of ``backward(T)``'s ``K_0, k_0, V_0, v_0`` as T grows,
         found by the structure-preserving doubling algorithm in one kernel launch.  ``max_iter`` caps the doubling steps
         (default 40), ``tol`` is the relative change of P at which it stops (default 4 fp32 ulps).  Returns a
         :class:`SteadyState`; never synchronises; sets ``last_status``.  An instance without a stabilising solution has
-        ``_hip.ST_NOT_STABILISING`` in its status and NaN outputs."""
+        ``_hip.ST_NOT_STABILISING`` in its status and NaN outputs.
+
+        ``differentiable=True``: when autograd is recording and a tensor operand requires grad, ``K, k, P, p`` are in the
+        autograd graph, with gradients from ``tfmpc_lqr_steady_state_vjp_f32`` (tfmpc/solvers/steady_state_grad.py,
+        DESIGN.md 3.10); the backward pass's per-instance status goes to ``last_grad_status``.  The outputs are the same
+        bits as without grad."""
         if not self.symmetric_cost:
             raise NotImplementedError("the steady state is served for a symmetric C only")
-        if tvlqr_grad.wants_grad(*self._sources):
-            raise NotImplementedError("gradients through the steady state are not served: call it under torch.no_grad() "
-                                      "or with operands that do not require grad")
+        grad = tvlqr_grad.wants_grad(*self._sources)
+        if grad and not differentiable:
+            raise NotImplementedError("gradients through the steady state are served with steady_state(differentiable=True) "
+                                      "or tfmpc.solvers.lqr_steady_state: otherwise call it under torch.no_grad() or with "
+                                      "operands that do not require grad")
         if max_iter is None:
             max_iter = 0
         elif int(max_iter) != max_iter or int(max_iter) < 1:
@@ -335,6 +342,20 @@ class LQR:
         n, m = self.state_size, self.action_size
         if n > 32 or m > 32:
             raise ValueError(f"the steady-state kernels serve n <= 32 and m <= 32, got n={n}, m={m}")
+        if grad:
+            from tfmpc.solvers import steady_state_grad
+            outs = steady_state_grad.SteadyStateFunction.apply(self, int(max_iter), float(tol),
+                                                               *steady_state_grad.graph_operands(self))
+        else:
+            outs = self._steady_state_launch(int(max_iter), float(tol))
+        if self.batch_size is None:
+            outs = tuple(t[0] for t in outs)
+        return SteadyState(*outs)
+
+    def _steady_state_launch(self, max_iter, tol):
+        """One tfmpc_lqr_steady_state_f32 launch on this solver's operands (0 / 0.0 select the kernel's defaults):
+        batched ``K, k, P, p, iterations, status``; sets ``last_status``."""
+        n, m = self.state_size, self.action_size
         lib = _hip.require_gpu()
         B = self.batch_size
         Bk = B if B is not None else 1
@@ -353,9 +374,7 @@ class LQR:
                                             _hip.ptr(iterations), _hip.ptr(status), _hip.stream())
         _hip.check(rc, "tfmpc_lqr_steady_state_f32")
         self.last_status = status
-        if B is None:
-            K, k, P, p, iterations, status = K[0], k[0], P[0], p[0], iterations[0], status[0]
-        return SteadyState(K, k, P, p, iterations, status)
+        return K, k, P, p, iterations, status
 
     # -- lqr.py:168-181 ------------------------------------------------------------
     def dump(self, file):
