@@ -243,6 +243,33 @@ int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
                         float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
                         int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------- control-limited TV-LQR gradients --------
+ * tfmpc_tvlqr_vjp_f32 at the optimum of the CONTROL-LIMITED problem, low <= u_t <= high.  low, high:
+ * [m] per (b, t) with a batch and a time stride in elements (0 = shared), +-inf allowed.  Control i of instance b is HELD
+ * at step t iff actions[b][t][i] equals low or high bit for bit (a forward that clips leaves the bound's bits on a
+ * clamped control).  There is no multiplier test: a control on its bound with a zero multiplier counts as held, as in
+ * Amos et al. 2018 (differentiable MPC).  Held controls have du = 0 in the adjoint: the adjoint solve runs on the model
+ * with column n + i of F_t, row and column n + i of C_t (unit diagonal) and entry n + i of the linear term taken out AS
+ * THE MODEL IS LOADED -- no masked copy exists; the workspace exceeds tfmpc_tvlqr_vjp_workspace_bytes by at most
+ * B T (4 + 8 m) + 4096 bytes.  All other arguments, outputs, stride-0 sums, status and NaN rules as tfmpc_tvlqr_vjp_f32.
+ * dlow, dhigh (optional): the gradient of the bound a held control sits on (low when it equals both), exactly 0 elsewhere,
+ * each with its own batch and time stride (0 sums over that axis, fixed order, no atomics).  clamp_mask[B][T] (optional):
+ * bit i = control i held at step t.  m <= 32; shapes as tfmpc_tvlqr_vjp_f32 otherwise (kernel_name: "unsupported"). */
+size_t tfmpc_tvlqr_box_vjp_workspace_bytes(int B, int n, int m, int T);
+const char *tfmpc_tvlqr_box_vjp_kernel_name(int n, int m, int T);
+int tfmpc_tvlqr_box_vjp_f32(int B, int n, int m, int T,
+                            const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                            const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+                            const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
+                            const float *low, long slow_b, long slow_t, const float *high, long shigh_b, long shigh_t,
+                            const float *states, const float *actions,
+                            const float *g_states, const float *g_actions, const float *g_costs,
+                            float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t,
+                            float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
+                            float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
+                            float *dlow, long sdlow_b, long sdlow_t, float *dhigh, long sdhigh_b, long sdhigh_t,
+                            uint32_t *clamp_mask, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------- infinite-horizon LQR --------
  * The stationary solution of tfmpc_lqr_*_f32's problem: A = F[:, :n], B = F[:, n:], Q = C_xx,
  * S = C_xu, R = C_uu (C symmetric).  P is the stabilising solution of the discrete algebraic Riccati equation, found by

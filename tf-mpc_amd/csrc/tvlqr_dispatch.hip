@@ -55,6 +55,34 @@ int run(const TvLqrArgs &a, bool bw, bool fw, void *stream)
 
 }  // namespace
 
+#define TFMPC_TVLQR_MODEL_PARAMS                                                                                    \
+    int B, int n, int m, int T, const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,         \
+        const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t, const float *Cfin, long sCfin_b, \
+        const float *cfin, long scfin_b
+#define TFMPC_TVLQR_MODEL Model{F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b}
+
+namespace tfmpc {
+
+int tvlqr_solve_masked_f32(TFMPC_TVLQR_MODEL_PARAMS, const float *x0, float *states, float *actions, float *costs,
+                           int32_t *status, const uint32_t *mask, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const Model md = TFMPC_TVLQR_MODEL;
+    int rc = check_model(B, n, m, T, md);
+    if (rc != TFMPC_OK || B == 0) return rc;
+    if (!x0 || !states || !costs || !actions) return TFMPC_ERR_ARG;
+    if (mask && m > 32) return TFMPC_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < tfmpc_tvlqr_workspace_bytes(B, n, m, T)) return TFMPC_ERR_WORKSPACE;
+    float *w = static_cast<float *>(workspace);
+    TvLqrArgs a = make_args(B, n, m, T, md);
+    a.x0 = x0;
+    a.K = w; a.k = w + (size_t)B * T * m * n; a.sK = (long)T * m * n; a.sk = (long)T * m;
+    a.states = states; a.actions = actions; a.costs = costs; a.status = status;
+    a.mask = mask;
+    return run(a, true, true, stream);
+}
+
+}  // namespace tfmpc
+
 extern "C" {
 
 size_t tfmpc_tvlqr_workspace_bytes(int B, int n, int m, int T)
@@ -71,12 +99,6 @@ const char *tfmpc_tvlqr_kernel_name(int n, int m, int T)
     if (tvlqr_generic_smem_bytes(n, m) > kMaxLdsBytes) return "unsupported";
     return "tv_generic_wave";
 }
-
-#define TFMPC_TVLQR_MODEL_PARAMS                                                                                    \
-    int B, int n, int m, int T, const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,         \
-        const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t, const float *Cfin, long sCfin_b, \
-        const float *cfin, long scfin_b
-#define TFMPC_TVLQR_MODEL Model{F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b}
 
 int tfmpc_tvlqr_backward_f32(TFMPC_TVLQR_MODEL_PARAMS, float *K, float *k, float *V, float *v, float *cst,
                              int32_t *status, void *stream)

@@ -68,10 +68,10 @@ __device__ inline TvSmem tv_carve(float *base, int n, int m)
     return s;
 }
 
-template <bool BACKWARD, bool FORWARD>
-__global__ __launch_bounds__(kWave) void tvlqr_generic_kernel(TvLqrArgs a)
+// MASKED: held controls (bit i of a.mask[b][t]) are taken out of the step's model after the LDS copy.
+template <bool BACKWARD, bool FORWARD, bool MASKED>
+__device__ __forceinline__ void tvlqr_generic_body(const TvLqrArgs &a, float *smem)
 {
-    extern __shared__ float smem[];
     const int b = blockIdx.x;
     const int lane = lane_id();
     const int n = a.n, m = a.m, d = n + m, T = a.T;
@@ -102,6 +102,14 @@ __global__ __launch_bounds__(kWave) void tvlqr_generic_kernel(TvLqrArgs a)
         for (int t = T - 1; t >= 0; --t) {
             load_model(t);
             wsync();
+            if (MASKED) {
+                const uint32_t w = a.mask[(size_t)b * T + t];
+                auto held = [&](int zi) { return zi >= n && (w >> (zi - n) & 1u); };
+                wave_for_2d(n, m, [&](int r, int j, int) { if (w >> j & 1u) s.F[r * ldd + n + j] = 0.0f; });
+                wave_for_2d(d, d, [&](int r, int j, int) { if (held(r) || held(j)) s.C[r * ldd + j] = (r == j) ? 1.0f : 0.0f; });
+                for (int r = lane; r < m; r += kWave) if (w >> r & 1u) s.c[n + r] = 0.0f;
+                wsync();
+            }
             // W = F_t^T V  [d][n]
             wave_matmul_mfma(d, n, n,
                         [&](int r, int k) { return s.F[k * ldd + r]; },
@@ -244,6 +252,20 @@ __global__ __launch_bounds__(kWave) void tvlqr_generic_kernel(TvLqrArgs a)
     if (a.status && lane == 0) a.status[b] = status;
 }
 
+template <bool BACKWARD, bool FORWARD>
+__global__ __launch_bounds__(kWave) void tvlqr_generic_kernel(TvLqrArgs a)
+{
+    extern __shared__ float smem[];
+    tvlqr_generic_body<BACKWARD, FORWARD, false>(a, smem);
+}
+
+// The fused solve on a masked model (tvlqr_solve_masked_f32).
+__global__ __launch_bounds__(kWave) void tvlqr_generic_masked_sweep(TvLqrArgs a)
+{
+    extern __shared__ float smem[];
+    tvlqr_generic_body<true, true, true>(a, smem);
+}
+
 template <bool BW, bool FW>
 int launch(const TvLqrArgs &a, hipStream_t stream)
 {
@@ -265,6 +287,16 @@ size_t tvlqr_generic_smem_bytes(int n, int m) { return tv_smem_floats(n, m) * si
 
 int tvlqr_generic_launch(const TvLqrArgs &a, bool backward, bool forward, hipStream_t stream)
 {
+    if (a.mask) {
+        if (!(backward && forward) || a.V || a.v || a.cst) return TFMPC_ERR_ARG;
+        const size_t smem = tvlqr_generic_smem_bytes(a.n, a.m);
+        if (smem > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
+        if (smem > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(tvlqr_generic_masked_sweep),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+            return TFMPC_ERR_LAUNCH;
+        hipLaunchKernelGGL(tvlqr_generic_masked_sweep, dim3(a.B), dim3(kWave), smem, stream, a);
+        return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+    }
     if (backward && forward) return launch<true, true>(a, stream);
     if (backward) return launch<true, false>(a, stream);
     return launch<false, true>(a, stream);

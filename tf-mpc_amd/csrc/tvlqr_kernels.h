@@ -24,6 +24,7 @@ struct TvLqrArgs {
     float *V, *v, *cst;           // optional value-function outputs [B][T][n][n], [B][T][n], [B][T]
     float *states, *actions, *costs;
     int32_t *status;
+    const uint32_t *mask;         // [B][T] or NULL; bit i: control i is held at step t (masked sweep)
 };
 
 __host__ __device__ inline const float *tv_at(const float *p, long sb, long st, int b, int t)
@@ -36,5 +37,15 @@ int tvlqr_mfma_launch(const TvLqrArgs &a, bool backward, bool forward, hipStream
 
 size_t tvlqr_generic_smem_bytes(int n, int m);
 int tvlqr_generic_launch(const TvLqrArgs &a, bool backward, bool forward, hipStream_t stream);
+
+// tfmpc_tvlqr_solve_f32 (same arguments, K = k = V = v = cst = NULL) on a MASKED model: for every set bit i of
+// mask[b][t], column n + i of F_t is read as zero, row and column n + i of C_t as zero with a unit diagonal, and
+// entry n + i of c_t as zero, so that row i of K_t and k_t[i] are exactly zero.  The mask is applied as the operands
+// are loaded; no masked copy of the model exists.  m <= 32.  mask == NULL is the plain solve.
+int tvlqr_solve_masked_f32(int B, int n, int m, int T, const float *F, long sF_b, long sF_t, const float *f, long sf_b,
+                           long sf_t, const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+                           const float *Cfin, long sCfin_b, const float *cfin, long scfin_b, const float *x0,
+                           float *states, float *actions, float *costs, int32_t *status, const uint32_t *mask,
+                           void *workspace, size_t workspace_bytes, void *stream);
 
 }  // namespace tfmpc

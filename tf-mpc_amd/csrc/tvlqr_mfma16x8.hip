@@ -71,8 +71,11 @@ struct StepOps { float F0[4], F1[4]; f32x4 C00, C01t, C11; };
 // index maps of every streamed load, and the fused solve with value outputs carries both phases' state: at 128 they
 // would spill, so they are sized for three (tests/test_tvlqr_cpu.py pins "no scratch" on every instantiation).
 #define TFMPC_TVLQR_EU ((EXACT && !(VALUE && FORWARD)) ? 4 : 3)
-template <bool BACKWARD, bool FORWARD, bool VALUE, bool EXACT, bool BF3>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(TFMPC_TVLQR_EU, TFMPC_TVLQR_EU))) void tvlqr_mfma16x8_kernel(TvLqrArgs a)
+// MASKED: the sweep of a model whose held controls (bit i of a.mask[b][t]) are taken out -- column
+// 16 + i of F~_t zero, row and column 16 + i of C~_t zero with a unit diagonal, c_u[i] zero, the device that pads small
+// shapes -- applied to the operand registers of a step right before they are used, never to the model in memory.
+template <bool BACKWARD, bool FORWARD, bool VALUE, bool EXACT, bool BF3, bool MASKED>
+__device__ __forceinline__ void tvlqr_mfma16x8_body(const TvLqrArgs &a)
 {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     const int b = blockIdx.x;
@@ -120,6 +123,21 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(TFMPC_TVL
                 }
             }
         };
+        // each operand slot has a fixed (row, column): a held control i clears this lane's F1 (column i), a held control
+        // k = 4q + r its C01t[r] (row k), and either leaves C11[r] the unit matrix's entry; w is uniform over the wave
+        auto mask_ops = [&](uint32_t w, StepOps &o) {
+            const bool ci = i < M && (w >> i & 1u);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * q + r;
+                const bool ck = k < M && (w >> k & 1u);
+                o.F1[r] = ci ? 0.0f : o.F1[r];
+                o.C01t[r] = ck ? 0.0f : o.C01t[r];
+                o.C11[r] = (k < M && (ci || ck)) ? ((i == k) ? 1.0f : 0.0f) : o.C11[r];
+            }
+        };
+        const uint32_t *mg = MASKED ? a.mask + (size_t)b * T : nullptr;
+        uint32_t wcur = MASKED ? mg[T - 1] : 0u, wnxt = 0u;
         StepOps cur, nxt;
         load_ops(T - 1, cur);
         // terminal value function: the final cost, or C_{T-1}[:n,:n], c_{T-1}[:n]; v lives in lanes i == 8
@@ -150,6 +168,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(TFMPC_TVL
         for (int t = T - 1; t >= 0; --t) {
             // step t-1's operands in flight while step t computes (clamped: unconditional, see the rollout ring)
             load_ops(t > 0 ? t - 1 : 0, nxt);
+            if (MASKED) {
+                wnxt = mg[t > 0 ? t - 1 : 0];
+                mask_ops(wcur, cur);
+            }
             ConstFrag Fc0{}, Fc1{};
             if (BF3) {
                 Fc0 = const_frag(f32x4{cur.F0[0], cur.F0[1], cur.F0[2], cur.F0[3]});
@@ -282,6 +304,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(TFMPC_TVL
             }
             lds_sync();
             cur = nxt;
+            if (MASKED) wcur = wnxt;
         }
         if (min_pivot_bits <= 0) status |= (min_pivot_bits == 0) ? TFMPC_ST_SINGULAR : TFMPC_ST_NOT_PD;
         if (VALUE && !(cst == cst)) status |= TFMPC_ST_NAN;
@@ -439,6 +462,19 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(TFMPC_TVL
     if (a.status && lane == 0) a.status[b] = status;
 }
 
+template <bool BACKWARD, bool FORWARD, bool VALUE, bool EXACT, bool BF3>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(TFMPC_TVLQR_EU, TFMPC_TVLQR_EU))) void tvlqr_mfma16x8_kernel(TvLqrArgs a)
+{
+    tvlqr_mfma16x8_body<BACKWARD, FORWARD, VALUE, EXACT, BF3, false>(a);
+}
+
+// The fused solve on a masked model (tvlqr_solve_masked_f32): the adjoint of a control-limited solve.
+template <bool EXACT, bool BF3>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(EXACT ? 4 : 3, EXACT ? 4 : 3))) void tvlqr_masked16x8_sweep(TvLqrArgs a)
+{
+    tvlqr_mfma16x8_body<true, true, false, EXACT, BF3, true>(a);
+}
+
 bool use_bf16x3() { return !option_is(kOptLqrMfma, "f32"); }
 
 template <bool BW, bool FW, bool VAL>
@@ -456,6 +492,19 @@ int launch(const TvLqrArgs &a, hipStream_t stream)
     return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
 }
 
+int launch_masked(const TvLqrArgs &a, hipStream_t stream)
+{
+    auto even = [](const void *p, long s) { return ((uintptr_t)p & 7) == 0 && (s & 1) == 0; };
+    const bool exact = a.n == N && a.m == M && even(a.F, a.sF_b) && even(a.F, a.sF_t) && even(a.K, a.sK);
+    const bool bf3 = use_bf16x3();
+    const dim3 grid(a.B), block(kWave);
+    if (exact && bf3) hipLaunchKernelGGL((tvlqr_masked16x8_sweep<true, true>), grid, block, 0, stream, a);
+    else if (exact) hipLaunchKernelGGL((tvlqr_masked16x8_sweep<true, false>), grid, block, 0, stream, a);
+    else if (bf3) hipLaunchKernelGGL((tvlqr_masked16x8_sweep<false, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((tvlqr_masked16x8_sweep<false, false>), grid, block, 0, stream, a);
+    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+}
+
 }  // namespace
 
 bool tvlqr_mfma_supported(int n, int m) { return n >= 1 && m >= 1 && n <= N && m <= M; }
@@ -463,6 +512,7 @@ bool tvlqr_mfma_supported(int n, int m) { return n >= 1 && m >= 1 && n <= N && m
 int tvlqr_mfma_launch(const TvLqrArgs &a, bool backward, bool forward, hipStream_t stream)
 {
     const bool value = a.V || a.v || a.cst;
+    if (a.mask) return (backward && forward && !value) ? launch_masked(a, stream) : TFMPC_ERR_ARG;
     if (backward && forward) return value ? launch<true, true, true>(a, stream) : launch<true, true, false>(a, stream);
     if (backward) return value ? launch<true, false, true>(a, stream) : launch<true, false, false>(a, stream);
     return launch<false, true, false>(a, stream);

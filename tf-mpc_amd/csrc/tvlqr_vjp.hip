@@ -18,6 +18,13 @@
 //                         record per instance, vjp_reduce_stage1 / stage2.  No atomics: the same call gives the same bits.
 // An instance whose adjoint solve reports TFMPC_ST_NOT_PD or TFMPC_ST_SINGULAR contributes NaN (its own rows, and
 // any reduction that includes it).  fp32 throughout; no scratch memory.
+//
+// tfmpc_tvlqr_box_vjp_f32 is the same VJP at a CONTROL-LIMITED optimum: a control that sits on a bound
+// (its bits equal low's or high's) is held, du = 0, in the adjoint.  box_fold_kernel also writes the held-set word per
+// (b, t) and zeroes the held entries of c~; the adjoint solve is the masked sweep (tvlqr_solve_masked_f32: the mask is
+// applied as the model is loaded, no masked copy exists); box_sweep_kernel runs the costate sweep on the UNMASKED model
+// and emits r_t[n + i] = (C_t dz_t + g_t + F_t^T dlam_{t+1})[n + i] of every held control into dlow or dhigh;
+// box_reduce_bounds sums them over the batch in a fixed order.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -57,6 +64,18 @@ struct VjpArgs {
     Out o[kKinds];
 };
 
+// The control-limited VJP's extra operands.  R_lo doubles as the fold's record of the unmasked g_u (read by the sweep
+// before it overwrites the entry with the bound's gradient).
+struct BoxArgs {
+    const float *low, *high;
+    long slo_b, slo_t, shi_b, shi_t;
+    uint32_t *mask, *mask_out;       // [B][T]: workspace, caller's (optional)
+    float *Rlo, *Rhi;                // [B][T][m]
+    Out olo, ohi;
+};
+
+__device__ inline bool same_bits(float x, float y) { return __float_as_uint(x) == __float_as_uint(y); }
+
 __device__ inline float poison_of(const int32_t *status, int b)
 {
     return (status[b] & (TFMPC_ST_NOT_PD | TFMPC_ST_SINGULAR)) ? __builtin_nanf("") : 0.0f;
@@ -65,14 +84,29 @@ __device__ inline float poison_of(const int32_t *status, int b)
 // ---- 1. fold -------------------------------------------------------------------------------------------------------
 // One wavefront per (b, t); t == T is the final step (rows < n).  With a cost gradient, C_t is staged in LDS by
 // coalesced loads (row stride d + 1) and each lane takes rows of C_t z_t + c_t.
-__global__ void __launch_bounds__(64) vjp_fold_kernel(VjpArgs a, float *ct, float *cT, float *Cfe, float *zer,
-                                                      const float *c_op, long sc_b, long sc_t, const float *Cfin_user)
+template <bool BOX>
+__device__ __forceinline__ void fold_body(const VjpArgs &a, float *ct, float *cT, float *Cfe, float *zer, const float *c_op,
+                                          long sc_b, long sc_t, const float *Cfin_user, const BoxArgs *bx)
 {
     extern __shared__ float sm[];
     const int n = a.n, m = a.m, T = a.T, d = n + m, L = threadIdx.x;
     const int b = (int)(blockIdx.x / (T + 1)), t = (int)(blockIdx.x % (T + 1));
     const float *x = a.states + ((size_t)b * (T + 1) + t) * n;
     if (t < T) {
+        uint32_t held = 0;
+        if (BOX) {                   // lane i < m (m <= 32): is control i on a bound, bit for bit?
+            bool on = false;
+            if (L < m) {
+                const float u = a.actions[((size_t)b * T + t) * m + L];
+                on = same_bits(u, tv_at(bx->low, bx->slo_b, bx->slo_t, b, t)[L]) ||
+                     same_bits(u, tv_at(bx->high, bx->shi_b, bx->shi_t, b, t)[L]);
+            }
+            held = (uint32_t)__ballot(on);
+            if (L == 0) {
+                bx->mask[(size_t)b * T + t] = held;
+                if (bx->mask_out) bx->mask_out[(size_t)b * T + t] = held;
+            }
+        }
         float *sC = sm, *sz = sm + (size_t)d * (d + 1);
         if (a.gc) {
             const float *Ct = tv_at(a.C, a.sC_b, a.sC_t, b, t);
@@ -91,6 +125,10 @@ __global__ void __launch_bounds__(64) vjp_fold_kernel(VjpArgs a, float *ct, floa
                 float r = tv_at(c_op, sc_b, sc_t, b, t)[i];
                 for (int j = 0; j < d; ++j) r = fmaf(Ci[j], sz[j], r);
                 g = fmaf(w, r, g);
+            }
+            if (BOX && i >= n) {
+                bx->Rlo[((size_t)b * T + t) * m + (i - n)] = g;
+                if (held >> (i - n) & 1u) g = 0.0f;
             }
             ct[((size_t)b * T + t) * d + i] = g;
         }
@@ -118,6 +156,19 @@ __global__ void __launch_bounds__(64) vjp_fold_kernel(VjpArgs a, float *ct, floa
     }
 }
 
+__global__ void __launch_bounds__(64) vjp_fold_kernel(VjpArgs a, float *ct, float *cT, float *Cfe, float *zer,
+                                                      const float *c_op, long sc_b, long sc_t, const float *Cfin_user)
+{
+    fold_body<false>(a, ct, cT, Cfe, zer, c_op, sc_b, sc_t, Cfin_user, nullptr);
+}
+
+__global__ void __launch_bounds__(64) box_fold_kernel(VjpArgs a, float *ct, float *cT, float *Cfe, float *zer,
+                                                      const float *c_op, long sc_b, long sc_t, const float *Cfin_user,
+                                                      BoxArgs bx)
+{
+    fold_body<true>(a, ct, cT, Cfe, zer, c_op, sc_b, sc_t, Cfin_user, &bx);
+}
+
 // ---- 3. costate sweep, per-instance gradients ------------------------------------------------------------------------
 __device__ inline void emit(const Out &o, int b, int t, bool first, int e, float v)
 {
@@ -126,7 +177,8 @@ __device__ inline void emit(const Out &o, int b, int t, bool first, int e, float
     *p = v;
 }
 
-__global__ void __launch_bounds__(kSweepThreads) vjp_sweep_kernel(VjpArgs a, bool store_factors)
+template <bool BOX>
+__device__ __forceinline__ void sweep_body(const VjpArgs &a, bool store_factors, const BoxArgs *bx)
 {
     extern __shared__ float sm[];
     const int n = a.n, m = a.m, T = a.T, d = n + m;
@@ -203,7 +255,30 @@ __global__ void __launch_bounds__(kSweepThreads) vjp_sweep_kernel(VjpArgs a, boo
             for (int r = L; r < 2 * n; r += kSweepThreads)
                 a.P[((size_t)b * T + t) * 2 * n + r] = r < n ? dlam[r] : lam[r - n];
         // lam_t = (C_t z_t + c_t)[:n] + F_t[:, :n]^T lam_{t+1};  dlam_t = (C_t dz_t + g_t)[:n] + F_t[:, :n]^T dlam_{t+1}
-        for (int r = L; r < 2 * n; r += kSweepThreads) {
+        // (BOX: m more rows in the same pass, r_t[n + i] = (C_t dz_t + g_t + F_t^T dlam_{t+1})[n + i] -- the gradient of the bound
+        // a held control sits on, low when it equals both; free controls and the other bound get 0)
+        const uint32_t held = BOX ? bx->mask[(size_t)b * T + t] : 0u;
+        for (int r = L; r < 2 * n + (BOX ? m : 0); r += kSweepThreads) {
+            if (BOX && r >= 2 * n) {
+                const int i = r - 2 * n;
+                float *rec = bx->Rlo + ((size_t)b * T + t) * m + i;
+                const bool on = held >> i & 1u;
+                const float *Ci = sC + (size_t)(n + i) * (d + 1);
+                float s = *rec;                          // the fold's unmasked g_u
+                for (int j = 0; j < d; ++j) s = fmaf(Ci[j], dz[j], s);
+                for (int k = 0; k < n; ++k) s = fmaf(sF[(size_t)k * d + n + i], dlam[k], s);
+                const bool at_low = same_bits(u[i], tv_at(bx->low, bx->slo_b, bx->slo_t, b, t)[i]);
+                const float vlo = ((on && at_low) ? s : 0.0f) + poison, vhi = ((on && !at_low) ? s : 0.0f) + poison;
+                if (bx->olo.p) {
+                    if (bx->olo.sb) emit(bx->olo, b, t, first, i, vlo);
+                    else *rec = vlo;
+                }
+                if (bx->ohi.p) {
+                    if (bx->ohi.sb) emit(bx->ohi, b, t, first, i, vhi);
+                    else bx->Rhi[((size_t)b * T + t) * m + i] = vhi;
+                }
+                continue;
+            }
             const int i = r % n;
             const bool adj = r >= n;
             const float *v = adj ? dz : z, *l = adj ? dlam : lam;
@@ -223,6 +298,53 @@ __global__ void __launch_bounds__(kSweepThreads) vjp_sweep_kernel(VjpArgs a, boo
             if (ox.sb) ox.p[(size_t)b * ox.sb + i] = dlam[i];
             else a.Pf[(size_t)b * n + i] = dlam[i];
         }
+}
+
+__global__ void __launch_bounds__(kSweepThreads) vjp_sweep_kernel(VjpArgs a, bool store_factors)
+{
+    sweep_body<false>(a, store_factors, nullptr);
+}
+
+__global__ void __launch_bounds__(kSweepThreads) box_sweep_kernel(VjpArgs a, bool store_factors, BoxArgs bx)
+{
+    sweep_body<true>(a, store_factors, &bx);
+}
+
+// Bound gradients shared by the batch: partial[(chunk * T + t) * m + e] = sum over the chunk's instances of R[b][t][e],
+// eight interleaved sub-sums per element combined in a fixed order (m <= 32); box_reduce_final sums the chunks.
+__global__ void __launch_bounds__(kRedThreads) box_reduce_bounds(const float *R, int B, int T, int m, float *partial)
+{
+    __shared__ float sub[kRedThreads];
+    const int chunk = blockIdx.x, t = blockIdx.y, e = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int b0 = chunk * kChunk, b1 = min(B, b0 + kChunk);
+    float s = 0.0f;
+    if (e < m)
+        for (int b = b0 + g; b < b1; b += kRedThreads / 32) s += R[((size_t)b * T + t) * m + e];
+    sub[threadIdx.x] = s;
+    __syncthreads();
+    if (g == 0 && e < m) {
+        for (int k = 1; k < kRedThreads / 32; ++k) s += sub[32 * k + e];
+        partial[((size_t)chunk * T + t) * m + e] = s;
+    }
+}
+
+// out[slot * st + e] = sum over the chunks (and, untimed, the steps) of partial[(chunk * T + t) * m + e]: one block per
+// (element, slot), 256 strided sub-sums and an LDS tree -- a fixed order, so the same call gives the same bits.
+__global__ void __launch_bounds__(kRedThreads) box_reduce_final(const float *partial, int chunks, int T, int m, bool timed,
+                                                                float *out, long st)
+{
+    __shared__ float sub[kRedThreads];
+    const int e = blockIdx.x, slot = blockIdx.y, tid = threadIdx.x;
+    const int t0 = timed ? slot : 0, nt = timed ? 1 : T, total = chunks * nt;
+    float s = 0.0f;
+    for (int q = tid; q < total; q += kRedThreads) s += partial[((size_t)(q / nt) * T + t0 + q % nt) * m + e];
+    sub[tid] = s;
+    __syncthreads();
+    for (int w = kRedThreads / 2; w > 0; w >>= 1) {
+        if (tid < w) sub[tid] += sub[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[(size_t)slot * st + e] = sub[0];
 }
 
 // ---- 4. batch reductions ---------------------------------------------------------------------------------------------
@@ -514,6 +636,38 @@ Layout layout(int B, int n, int m, int T)
     return L;
 }
 
+struct BoxLayout { size_t mask, Rlo, Rhi, total; };   // offsets in floats, after the plain VJP's workspace
+
+BoxLayout box_layout(int B, int n, int m, int T)
+{
+    BoxLayout L{};
+    size_t o = layout(B, n, m, T).total;
+    L.mask = o; o += up64((size_t)B * T);
+    L.Rlo = o; o += up64((size_t)B * T * m);
+    L.Rhi = o; o += up64((size_t)B * T * m);
+    L.total = o;
+    return L;
+}
+
+struct BoxCall {
+    const float *low, *high;
+    long slo_b, slo_t, shi_b, shi_t;
+    float *dlow, *dhigh;
+    long sdlo_b, sdlo_t, sdhi_b, sdhi_t;
+    uint32_t *clamp_mask;
+};
+
+int vjp_impl(int B, int n, int m, int T,
+             const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+             const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+             const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
+             const float *states, const float *actions,
+             const float *g_states, const float *g_actions, const float *g_costs,
+             float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t,
+             float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
+             float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
+             int32_t *status, void *workspace, size_t workspace_bytes, void *stream, const BoxCall *box);
+
 }  // namespace
 
 extern "C" {
@@ -524,16 +678,57 @@ size_t tfmpc_tvlqr_vjp_workspace_bytes(int B, int n, int m, int T)
     return layout(B, n, m, T).total * sizeof(float);
 }
 
-int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
-                        const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
-                        const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
-                        const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
-                        const float *states, const float *actions,
-                        const float *g_states, const float *g_actions, const float *g_costs,
-                        float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t,
-                        float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
-                        float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
-                        int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
+#define TFMPC_VJP_PARAMS_HEAD                                                                                      \
+    int B, int n, int m, int T, const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,          \
+        const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t, const float *Cfin, long sCfin_b, \
+        const float *cfin, long scfin_b
+#define TFMPC_VJP_PARAMS_TAIL                                                                                      \
+    const float *states, const float *actions, const float *g_states, const float *g_actions, const float *g_costs, \
+        float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t, float *dC, long sdC_b, long sdC_t,    \
+        float *dc, long sdc_b, long sdc_t, float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0,    \
+        long sdx0_b
+#define TFMPC_VJP_HEAD B, n, m, T, F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b
+#define TFMPC_VJP_TAIL                                                                                             \
+    states, actions, g_states, g_actions, g_costs, dF, sdF_b, sdF_t, df, sdf_b, sdf_t, dC, sdC_b, sdC_t, dc, sdc_b, \
+        sdc_t, dCfin, sdCfin_b, dcfin, sdcfin_b, dx0, sdx0_b
+
+int tfmpc_tvlqr_vjp_f32(TFMPC_VJP_PARAMS_HEAD, TFMPC_VJP_PARAMS_TAIL, int32_t *status, void *workspace,
+                        size_t workspace_bytes, void *stream)
+{
+    return vjp_impl(TFMPC_VJP_HEAD, TFMPC_VJP_TAIL, status, workspace, workspace_bytes, stream, nullptr);
+}
+
+size_t tfmpc_tvlqr_box_vjp_workspace_bytes(int B, int n, int m, int T)
+{
+    if (B <= 0 || n <= 0 || m <= 0 || T <= 0) return 0;
+    return box_layout(B, n, m, T).total * sizeof(float);
+}
+
+const char *tfmpc_tvlqr_box_vjp_kernel_name(int n, int m, int T)
+{
+    (void)T;
+    if (n <= 0 || m <= 0) return "invalid";
+    if (tvlqr_mfma_supported(n, m)) return (n == 16 && m == 8) ? "tv_masked_16x8" : "tv_masked_16x8 (zero-padded)";
+    if (m > 32 || tvlqr_generic_smem_bytes(n, m) > kMaxLdsBytes || sweep_smem_bytes(n, m) > kMaxLdsBytes) return "unsupported";
+    return "tv_masked_generic_wave";
+}
+
+int tfmpc_tvlqr_box_vjp_f32(TFMPC_VJP_PARAMS_HEAD, const float *low, long slow_b, long slow_t, const float *high,
+                            long shigh_b, long shigh_t, TFMPC_VJP_PARAMS_TAIL, float *dlow, long sdlow_b, long sdlow_t,
+                            float *dhigh, long sdhigh_b, long sdhigh_t, uint32_t *clamp_mask, int32_t *status,
+                            void *workspace, size_t workspace_bytes, void *stream)
+{
+    const BoxCall box{low, high, slow_b, slow_t, shigh_b, shigh_t, dlow, dhigh, sdlow_b, sdlow_t, sdhigh_b, sdhigh_t,
+                      clamp_mask};
+    return vjp_impl(TFMPC_VJP_HEAD, TFMPC_VJP_TAIL, status, workspace, workspace_bytes, stream, &box);
+}
+
+}  // extern "C"
+
+namespace {
+
+int vjp_impl(TFMPC_VJP_PARAMS_HEAD, TFMPC_VJP_PARAMS_TAIL, int32_t *status, void *workspace, size_t workspace_bytes,
+             void *stream, const BoxCall *box)
 {
     if (B < 0 || n <= 0 || m <= 0 || T <= 0) return TFMPC_ERR_ARG;
     if (!tvlqr_mfma_supported(n, m) && tvlqr_generic_smem_bytes(n, m) > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
@@ -544,11 +739,18 @@ int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
     if (T > 65535) return TFMPC_ERR_UNSUPPORTED;                   // per-step reduction slots are one grid axis
     if ((size_t)B * (T + 1) > 0x7fffffffu) return TFMPC_ERR_UNSUPPORTED;   // fold: one block per (b, t)
     if (sweep_smem_bytes(n, m) > kMaxLdsBytes || fold_smem_bytes(n, m) > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
+    if (box) {
+        if (m > 32) return TFMPC_ERR_UNSUPPORTED;                  // one held-set word per step
+        if (!box->low || !box->high) return TFMPC_ERR_ARG;
+        for (long s : {box->slo_b, box->slo_t, box->shi_b, box->shi_t, box->sdlo_b, box->sdlo_t, box->sdhi_b, box->sdhi_t})
+            if (s < 0) return TFMPC_ERR_ARG;
+    }
     for (long s : {sF_b, sF_t, sf_b, sf_t, sC_b, sC_t, sc_b, sc_t, sCfin_b, scfin_b, sdF_b, sdF_t, sdf_b, sdf_t,
                    sdC_b, sdC_t, sdc_b, sdc_t, sdCfin_b, sdcfin_b, sdx0_b})
         if (s < 0) return TFMPC_ERR_ARG;
     const Layout L = layout(B, n, m, T);
-    if (!workspace || workspace_bytes < L.total * sizeof(float)) return TFMPC_ERR_WORKSPACE;
+    const BoxLayout XL = box ? box_layout(B, n, m, T) : BoxLayout{};
+    if (!workspace || workspace_bytes < (box ? XL.total : L.total) * sizeof(float)) return TFMPC_ERR_WORKSPACE;
     const int d = n + m;
     hipStream_t s = static_cast<hipStream_t>(stream);
     float *w = static_cast<float *>(workspace);
@@ -573,23 +775,44 @@ int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
     Out outs[kKinds] = {{dF, sdF_b, sdF_t}, {df, sdf_b, sdf_t}, {dC, sdC_b, sdC_t}, {dc, sdc_b, sdc_t},
                         {dCfin, sdCfin_b, 0}, {dcfin, sdcfin_b, 0}, {dx0, sdx0_b, 0}};
     for (int k = 0; k < kKinds; ++k) a.o[k] = outs[k];
+    BoxArgs bx{};
+    if (box) {
+        bx.low = box->low; bx.slo_b = box->slo_b; bx.slo_t = box->slo_t;
+        bx.high = box->high; bx.shi_b = box->shi_b; bx.shi_t = box->shi_t;
+        bx.mask = reinterpret_cast<uint32_t *>(w + XL.mask); bx.mask_out = box->clamp_mask;
+        bx.Rlo = w + XL.Rlo; bx.Rhi = w + XL.Rhi;
+        bx.olo = Out{box->dlow, box->sdlo_b, box->sdlo_t};
+        bx.ohi = Out{box->dhigh, box->sdhi_b, box->sdhi_t};
+    }
 
     // 1. fold
     {
         const size_t smem = fold_smem_bytes(n, m);
-        if (!allow_lds(vjp_fold_kernel, smem)) return TFMPC_ERR_LAUNCH;
-        hipLaunchKernelGGL(vjp_fold_kernel, dim3((unsigned)((size_t)B * (T + 1))), dim3(64), smem, s, a, w + L.ct, w + L.cT,
-                           w + L.Cfe, w + L.zer, c, sc_b, sc_t, Cfin);
+        const dim3 grid((unsigned)((size_t)B * (T + 1)));
+        if (box) {
+            if (!allow_lds(box_fold_kernel, smem)) return TFMPC_ERR_LAUNCH;
+            hipLaunchKernelGGL(box_fold_kernel, grid, dim3(64), smem, s, a, w + L.ct, w + L.cT, w + L.Cfe, w + L.zer, c, sc_b,
+                               sc_t, Cfin, bx);
+        } else {
+            if (!allow_lds(vjp_fold_kernel, smem)) return TFMPC_ERR_LAUNCH;
+            hipLaunchKernelGGL(vjp_fold_kernel, grid, dim3(64), smem, s, a, w + L.ct, w + L.cT, w + L.Cfe, w + L.zer, c, sc_b,
+                               sc_t, Cfin);
+        }
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
     }
     // 2. adjoint solve: c~ per (b, t), f~ = 0 (shared), explicit final cost, x~0 = 0
     {
         const float *Cf_adj = a.dflt ? w + L.Cfe : Cfin;
         const long sCf_adj = a.dflt ? a.sCf_b : sCfin_b;
-        int rc = tfmpc_tvlqr_solve_f32(B, n, m, T, F, sF_b, sF_t, w + L.zer, 0, 0, C, sC_b, sC_t, w + L.ct, (long)T * d,
-                                       d, Cf_adj, sCf_adj, w + L.cT, n, w + L.zer, w + L.dS, w + L.dA, w + L.dcost,
-                                       nullptr, nullptr, nullptr, nullptr, nullptr, status, w + L.solve, L.solve_bytes,
-                                       stream);
+        int rc;
+        if (box)                     // the held controls taken out of the model as it is loaded
+            rc = tvlqr_solve_masked_f32(B, n, m, T, F, sF_b, sF_t, w + L.zer, 0, 0, C, sC_b, sC_t, w + L.ct, (long)T * d, d,
+                                        Cf_adj, sCf_adj, w + L.cT, n, w + L.zer, w + L.dS, w + L.dA, w + L.dcost, status,
+                                        bx.mask, w + L.solve, L.solve_bytes, stream);
+        else
+            rc = tfmpc_tvlqr_solve_f32(B, n, m, T, F, sF_b, sF_t, w + L.zer, 0, 0, C, sC_b, sC_t, w + L.ct, (long)T * d, d,
+                                       Cf_adj, sCf_adj, w + L.cT, n, w + L.zer, w + L.dS, w + L.dA, w + L.dcost, nullptr,
+                                       nullptr, nullptr, nullptr, nullptr, status, w + L.solve, L.solve_bytes, stream);
         if (rc != TFMPC_OK) return rc;
     }
     // for the sweep, the final cost's linear term is the forward's: default c_{T-1}[:n] (contiguous in c at stride 1)
@@ -601,8 +824,13 @@ int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
     const bool reduce_F = (dF && !sdF_b) || (df && !sdf_b);
     {
         const size_t smem = sweep_smem_bytes(n, m);
-        if (!allow_lds(vjp_sweep_kernel, smem)) return TFMPC_ERR_LAUNCH;
-        hipLaunchKernelGGL(vjp_sweep_kernel, dim3(B), dim3(kSweepThreads), smem, s, sw, reduce_F);
+        if (box) {
+            if (!allow_lds(box_sweep_kernel, smem)) return TFMPC_ERR_LAUNCH;
+            hipLaunchKernelGGL(box_sweep_kernel, dim3(B), dim3(kSweepThreads), smem, s, sw, reduce_F, bx);
+        } else {
+            if (!allow_lds(vjp_sweep_kernel, smem)) return TFMPC_ERR_LAUNCH;
+            hipLaunchKernelGGL(vjp_sweep_kernel, dim3(B), dim3(kSweepThreads), smem, s, sw, reduce_F);
+        }
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
     }
     // 4. shared gradients
@@ -639,7 +867,20 @@ int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
                            1, nEs[k], o.p, 0L);
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
     }
+    if (box) {                       // bound gradients shared by the batch: the sweep's records, chunks, then steps
+        const Out bo[2] = {bx.olo, bx.ohi};
+        const float *rec[2] = {bx.Rlo, bx.Rhi};
+        for (int k = 0; k < 2; ++k) {
+            if (!bo[k].p || bo[k].sb) continue;
+            hipLaunchKernelGGL(box_reduce_bounds, dim3(chunks, T), dim3(kRedThreads), 0, s, rec[k], B, T, m, partial);
+            if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
+            const bool timed = bo[k].st != 0;
+            hipLaunchKernelGGL(box_reduce_final, dim3(m, timed ? T : 1), dim3(kRedThreads), 0, s, partial, chunks, T, m, timed,
+                               bo[k].p, bo[k].st);
+            if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
+        }
+    }
     return TFMPC_OK;
 }
 
-}  // extern "C"
+}  // namespace
