@@ -81,10 +81,11 @@ def autograd_grads(F, f, C, c, x0, Cfin, cfin, gx, gu, gcost, dtype=torch.float6
     return got
 
 
-def closed_form(F, f, C, c, x0, Cfin, cfin, gx, gu, gcost, dtype=torch.float64):
+def closed_form(F, f, C, c, x0, Cfin, cfin, gx, gu, gcost, dtype=torch.float64, parts=False):
     """The adjoint of DESIGN.md §3.8 (fp64 is the oracle; fp32 is the error budget of the algorithm the kernels run):
     fold, adjoint solve, costates, outer products.  gx[B,T+1,n], gu[B,T,m], gcost[B,T+1] (each may be None = zero)
-    -> dict of gradients with the operands' [B, T, ...] shapes.
+    -> dict of gradients with the operands' [B, T, ...] shapes.  ``parts=True`` -> (that dict, the factors the
+    gradients are products of: z, dz [B,T,d]; lam, dlam [B,T,n] (of step t + 1); gcost [B,T+1]; x_T, dx_T, dlam_0 [B,n]).
 
     In fp32 this algorithm is less accurate than autograd through ``solve`` for the costate-built gradients F, f and
     x0: on the seeded workloads of tests/test_tvlqr_grad_gpu.py (T = 2 / 20 / 50) the median ratio of the errors is
@@ -130,4 +131,6 @@ def closed_form(F, f, C, c, x0, Cfin, cfin, gx, gu, gcost, dtype=torch.float64):
         out["c"][:, T - 1, :n] += dcf
     else:
         out.update(Cfin=dCf, cfin=dcf)
+    if parts:
+        return out, dict(z=z, dz=dz, lam=lam1, dlam=dlam1, gcost=gcost, x_T=xT, dx_T=dxT, dlam_0=dlam[0])
     return out
