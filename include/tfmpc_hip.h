@@ -243,6 +243,35 @@ int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
                         float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
                         int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------- gradients of the Riccati recursion --------
+ * Vector-Jacobian product of tfmpc_tvlqr_backward_f32: given the recursion's K[B][T][m][n], k[B][T][m],
+ * V[B][T][n][n], v[B][T][n] and status[B] (fwd_status), and upstream gradients gK, gk, gV, gv, gconst[B][T] of the same
+ * layouts (each NULL = zero), writes the gradients of <gK, K> + <gk, k> + <gV, V> + <gv, v> + <gconst, const> with
+ * respect to F, f, C, c, Cfin and cfin.  Model operands, strides and the final cost as in tfmpc_tvlqr_backward_f32
+ * (Cfin = cfin = NULL: the default final cost, whose gradient then lands in dC[T-1][:n,:n] and dc[T-1][:n]; dCfin / dcfin
+ * must be NULL).  One sweep forward in time carries the adjoints of V_t, v_t, const_t; it reads the model and K, k, V, v
+ * only (the recursion is not recomputed) and eliminates Q_uu = C_t,uu + F_t,u' V_{t+1} F_t,u once per step without
+ * pivoting (a non-positive pivot: TFMPC_ST_NOT_PD).  Outputs, their batch and time strides, stride-0 sums (time: in the
+ * sweep, in time order; batch: per-instance records in the workspace and a fixed-order two-stage sum, no atomics --
+ * repeated calls give identical bits), NULL outputs and the symmetric dC, dCfin as in tfmpc_tvlqr_vjp_f32.  status[B]
+ * (required) gets the forward's status where it was flagged, else this sweep's; a flagged instance has NaN in its own
+ * gradient rows and in every batch-summed gradient.  workspace: tfmpc_tvlqr_backward_vjp_workspace_bytes(B, n, m, T) bytes
+ * serve any choice of summed outputs (NULL is fine when no output is summed over a batch of more than one).
+ * n <= 16, m <= 16: 16-wide LDS tiles; n <= 32, m <= 16: 32-wide; beyond: TFMPC_ERR_UNSUPPORTED (kernel_name:
+ * "unsupported").  One wave per instance, every product on the f32 matrix cores.  B == 0 is a no-op. */
+size_t tfmpc_tvlqr_backward_vjp_workspace_bytes(int B, int n, int m, int T);
+const char *tfmpc_tvlqr_backward_vjp_kernel_name(int n, int m, int T);
+int tfmpc_tvlqr_backward_vjp_f32(int B, int n, int m, int T,
+                                 const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                                 const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+                                 const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
+                                 const float *K, const float *k, const float *V, const float *v, const int32_t *fwd_status,
+                                 const float *gK, const float *gk, const float *gV, const float *gv, const float *gconst,
+                                 float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t,
+                                 float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
+                                 float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b,
+                                 int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------- control-limited TV-LQR gradients --------
  * tfmpc_tvlqr_vjp_f32 at the optimum of the CONTROL-LIMITED problem, low <= u_t <= high.  low, high:
  * [m] per (b, t) with a batch and a time stride in elements (0 = shared), +-inf allowed.  Control i of instance b is HELD

@@ -175,9 +175,29 @@ class LQR:
         return x0.contiguous()
 
     # -- lqr.py:59-129 -------------------------------------------------------------
-    def backward(self, T):
-        lib = _hip.require_gpu()
+    def backward(self, T, differentiable=False):
+        """``differentiable=True``: when autograd is recording and a tensor operand requires grad, the returned
+        ``Policy`` / ``ValueFn`` hold tensors in the autograd graph (the same bits: this class's own kernel runs the
+        recursion), with gradients summed over the horizon from ``tfmpc_tvlqr_backward_vjp_f32`` at time stride 0
+        (tfmpc/solvers/tvlqr_backward_grad.py)."""
         T = int(T)
+        if differentiable and tvlqr_grad.wants_grad(*self._sources):
+            if not self.symmetric_cost:
+                raise NotImplementedError("gradients of the Riccati recursion are served for a symmetric C only")
+            from tfmpc.solvers import steady_state_grad, tvlqr_backward_grad
+            from tfmpc.solvers.tvlqr import TimeVaryingLQR
+            problem = tvlqr_grad.Problem(lambda: self._backward_launch(T), lambda: TimeVaryingLQR.from_lqr(self, T), False, self)
+            K, k, V, v, const = tvlqr_backward_grad.BackwardFunction.apply(problem, *steady_state_grad.graph_operands(self),
+                                                                           None, None)
+        else:
+            K, k, V, v, const, _ = self._backward_launch(T)
+        if self.batch_size is None:
+            K, k, V, v, const = K[0], k[0], V[0], v[0], const[0]
+        return Policy(K, k), ValueFn(V, v, const)
+
+    def _backward_launch(self, T):
+        """One tfmpc_lqr_backward launch: batched ``K, k, V, v, const, status``; sets ``last_status``."""
+        lib = _hip.require_gpu()
         n, m = self.state_size, self.action_size
         B = self.batch_size
         Bk = B or 1
@@ -193,9 +213,7 @@ class LQR:
                                         _hip.ptr(status), _hip.stream())
         _hip.check(rc, "tfmpc_lqr_backward_f32")
         self.last_status = status
-        if B is None:
-            K, k, V, v, const = K[0], k[0], V[0], v[0], const[0]
-        return Policy(K, k), ValueFn(V, v, const)
+        return K, k, V, v, const, status
 
     # -- lqr.py:131-161 ------------------------------------------------------------
     def forward(self, policy, x0, T):

@@ -170,7 +170,23 @@ class TimeVaryingLQR:
         return LQR._resolve_batch(self, x0)
 
     # -- backward / forward / solve ------------------------------------------------------
-    def backward(self):
+    def backward(self, differentiable=False):
+        """The Riccati recursion: ``(Policy, ValueFn)``.  ``differentiable=True``: when autograd is recording and a tensor
+        operand requires grad, their tensors are in the autograd graph, with gradients from
+        ``tfmpc_tvlqr_backward_vjp_f32`` (tfmpc/solvers/tvlqr_backward_grad.py); the backward pass's
+        per-instance status goes to ``last_grad_status``.  The outputs are the same bits as without grad."""
+        if differentiable and tvlqr_grad.wants_grad(*self._sources):
+            from tfmpc.solvers import tvlqr_backward_grad as bgrad
+            problem = tvlqr_grad.Problem(self._backward_launch, lambda: self, True, self)
+            K, k, V, v, const = bgrad.BackwardFunction.apply(problem, *bgrad.tv_graph_operands(self))
+        else:
+            K, k, V, v, const, _ = self._backward_launch()
+        if self.batch_size is None:
+            K, k, V, v, const = K[0], k[0], V[0], v[0], const[0]
+        return Policy(K, k), ValueFn(V, v, const)
+
+    def _backward_launch(self):
+        """One tfmpc_tvlqr_backward_f32 launch: batched ``K, k, V, v, const, status``; sets ``last_status``."""
         lib = _hip.require_gpu()
         n, m, T = self.state_size, self.action_size, self.horizon
         B = self.batch_size
@@ -186,9 +202,7 @@ class TimeVaryingLQR:
                                           _hip.ptr(v), _hip.ptr(const), _hip.ptr(status), _hip.stream())
         _hip.check(rc, "tfmpc_tvlqr_backward_f32")
         self.last_status = status
-        if B is None:
-            K, k, V, v, const = K[0], k[0], V[0], v[0], const[0]
-        return Policy(K, k), ValueFn(V, v, const)
+        return K, k, V, v, const, status
 
     def forward(self, policy, x0):
         lib = _hip.require_gpu()
