@@ -162,7 +162,7 @@ def test_the_steady_state_vjp_kernels_use_no_scratch():
         subprocess.run([check_ring_waits.hipcc_path(), *check_ring_waits.FLAGS, "--cuda-device-only", "-S", path, "-o", out], check=True,
                        capture_output=True)
         text = open(out).read()
-    found = re.findall(r"\.name:\s+(\S*ss_vjp_\S*)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
+    found = re.findall(r"\.name:\s+(\S*(?:ss_vjp_|batch_sum_)\S*)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
                        r"\s+\.vgpr_spill_count:\s+(\d+)", text)
     assert len([f for f in found if "ss_vjp_kernel" in f[0]]) == 2, found
     assert len(found) == 4, found

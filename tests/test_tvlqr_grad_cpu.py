@@ -126,7 +126,7 @@ def test_the_vjp_kernels_use_no_scratch():
         subprocess.run([check_ring_waits.hipcc_path(), *check_ring_waits.FLAGS, "--cuda-device-only", "-S", path, "-o", out], check=True,
                        capture_output=True)
         text = open(out).read()
-    found = re.findall(r"\.name:\s+(\S*vjp_\S*)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
+    found = re.findall(r"\.name:\s+(\S*(?:vjp_|batch_sum_)\S*)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
                        r"\s+\.vgpr_spill_count:\s+(\d+)", text)
     assert len(found) == 7, found
     for name, private, vgprs, spills in found:

@@ -41,20 +41,6 @@ struct SsArgs {
     int32_t *iterations, *status;
 };
 
-// X <- (X + X') / 2 in place; the pair (i, j), (j, i) belongs to one lane
-__device__ __forceinline__ void symmetrise(float *X, int ld, int n)
-{
-    wave_for_2d(n, n, [&](int i, int j, int) {
-        if (i < j) {
-            const float s = 0.5f * (X[i * ld + j] + X[j * ld + i]);
-            X[i * ld + j] = s;
-            X[j * ld + i] = s;
-        }
-    });
-}
-
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= FLT_MAX; }
-
 template <int NP>
 __global__ __launch_bounds__(kWave) void lqr_steady_state_kernel(SsArgs a)
 {
@@ -173,11 +159,7 @@ __global__ __launch_bounds__(kWave) void lqr_steady_state_kernel(SsArgs a)
                          [&](int i, int j, float x) { sT1[i * LDN + j] = x; });
         wave_matmul_mfma(n, n, n, [&](int i, int kk) { return sH[i * LDN + kk]; }, Am, zero,
                          [&](int i, int j, float x) { sT2[i * LDN + j] = x; });
-        for (int i = lane; i < n; i += kWave) {
-            float s = 0.0f;
-            for (int j = 0; j < n; ++j) s = fmaf(sH[i * LDN + j], sf[j], s);
-            pf[i] = s;
-        }
+        wave_matvec(n, n, [&](int i, int j) { return sH[i * LDN + j]; }, [&](int j) { return sf[j]; }, [&](int i, float s) { pf[i] = s; });
         wsync();
         // aug = [R + B'PB | B'PA + S' | c_u | B']  (m rows)
         wave_matmul_mfma(m, m, n, [&](int i, int kk) { return Bm(kk, i); }, [&](int kk, int j) { return sT1[kk * LDN + j]; },
@@ -221,11 +203,8 @@ __global__ __launch_bounds__(kWave) void lqr_steady_state_kernel(SsArgs a)
         for (int i = lane; i < n; i += kWave) pv[i] = aug[i * LDA + n];
         wsync();
         // k = kv - Z (P f + p)
-        for (int r = lane; r < m; r += kWave) {
-            float s = 0.0f;
-            for (int j = 0; j < n; ++j) s = fmaf(sG[r * LDN + j], pf[j] + pv[j], s);
-            kv[r] = kv[r] - s;
-        }
+        wave_matvec(m, n, [&](int r, int j) { return sG[r * LDN + j]; }, [&](int j) { return pf[j] + pv[j]; },
+                    [&](int r, float s) { kv[r] = kv[r] - s; });
         wsync();
         bool bad = false;
         wave_for_2d(n, n, [&](int i, int j, int) { bad |= !finite(sH[i * LDN + j]); });

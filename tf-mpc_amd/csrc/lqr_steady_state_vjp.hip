@@ -19,14 +19,14 @@
 // Layout as the forward (lqr_steady_state.hip): NP = 16 serves n, m <= 16, NP = 32 serves n, m <= 32, every matrix in
 // the wave's LDS slice, every product on v_mfma_f32_16x16x4_f32 (wave_ops.h mfma_matmul, strict fp32).  A gradient
 // whose batch stride is 0 is summed over the batch: the instance kernel writes per-instance records into the workspace,
-// then ss_vjp_reduce_stage1 (fixed-order sums over chunks of instances) and ss_vjp_reduce_stage2 (fixed-order sum of
-// the chunks) write the output.  No atomics: the same call gives the same bits.
+// then the shared batch sum (batch_sum.h: chunks of 64 instances, tree over the chunks) writes the output.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 #include <cstdint>
 
 #include "../../include/tfmpc_hip.h"
+#include "batch_sum.h"
 #include "wave_ops.h"
 
 namespace tfmpc {
@@ -36,8 +36,7 @@ namespace {
 constexpr int kVjpMaxIter = 40;
 constexpr float kVjpTol = 4.0f * FLT_EPSILON;
 constexpr float kPhiZero = 1e-3f;
-constexpr int kRedChunk = 64;          // instances per stage-1 block
-constexpr int kRedThreads = 256;
+constexpr int kRedChunk = 64;          // instances per stage-1 block of the batch sum
 enum { kOutF, kOutf, kOutC, kOutc, kOuts };
 
 struct VjpOut {
@@ -56,8 +55,6 @@ struct SsVjpArgs {
     VjpOut o[kOuts];
     int32_t *status;
 };
-
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= FLT_MAX; }
 
 template <int NP>
 __global__ __launch_bounds__(kWave) void ss_vjp_kernel(SsVjpArgs a)
@@ -95,11 +92,8 @@ __global__ __launch_bounds__(kWave) void ss_vjp_kernel(SsVjpArgs a)
                          [&](int i, int j, float x) { sPB[i * LDN + j] = x; });
         wave_matmul_mfma(n, n, m, Bm, [&](int kk, int j) { return sK[kk * LDN + j]; }, Am,
                          [&](int i, int j, float x) { sAcl[i * LDN + j] = x; });
-        for (int i = lane; i < n; i += kWave) {
-            float s = 0.0f;
-            for (int j = 0; j < n; ++j) s = fmaf(sP[i * LDN + j], vf[j], s);
-            vw[i] = s + vp[i];
-        }
+        wave_matvec(n, n, [&](int i, int j) { return sP[i * LDN + j]; }, [&](int j) { return vf[j]; },
+                    [&](int i, float s) { vw[i] = s + vp[i]; });
         wsync();
         // aug = [R + B'PB | I | gk]  (m rows), R + B'PB symmetrised as in the forward
         wave_matmul_mfma(m, m, n, [&](int i, int kk) { return Bm(kk, i); }, [&](int kk, int j) { return sPB[kk * LDN + j]; },
@@ -108,13 +102,7 @@ __global__ __launch_bounds__(kWave) void ss_vjp_kernel(SsVjpArgs a)
             aug[r * LDD + m + j] = j < m ? (r == j ? 1.0f : 0.0f) : (a.gk ? a.gk[(size_t)b * m + r] : 0.0f);
         });
         wsync();
-        wave_for_2d(m, m, [&](int i, int j, int) {
-            if (i < j) {
-                const float s = 0.5f * (aug[i * LDD + j] + aug[j * LDD + i]);
-                aug[i * LDD + j] = s;
-                aug[j * LDD + i] = s;
-            }
-        });
+        symmetrise(aug, LDD, m);
         wsync();
         if (wave_gauss_jordan<false>(aug, LDD, m, 2 * m + 1, fac, fac)) status |= TFMPC_ST_NOT_PD;
     }
@@ -124,12 +112,10 @@ __global__ __launch_bounds__(kWave) void ss_vjp_kernel(SsVjpArgs a)
         for (int r = lane; r < m; r += kWave) vkap[r] = aug[r * LDD + 2 * m];
         wsync();
         // wbar = -B kappa;  T1 = [I - A_cl | gp + wbar]  (n rows)
-        for (int i = lane; i < n; i += kWave) {
-            float s = 0.0f;
-            for (int r = 0; r < m; ++r) s = fmaf(Bm(i, r), vkap[r], s);
+        wave_matvec(n, m, Bm, [&](int r) { return vkap[r]; }, [&](int i, float s) {
             vwbar[i] = -s;
             sT1[i * LDN + n] = (a.gp ? a.gp[(size_t)b * n + i] : 0.0f) - s;
-        }
+        });
         wave_for_2d(n, n, [&](int i, int j, int) { sT1[i * LDN + j] = (i == j ? 1.0f : 0.0f) - sAcl[i * LDN + j]; });
         wsync();
         if (wave_gauss_jordan<true>(sT1, LDN, n, n + 1, fac, fac)) status |= TFMPC_ST_SINGULAR;
@@ -148,11 +134,8 @@ __global__ __launch_bounds__(kWave) void ss_vjp_kernel(SsVjpArgs a)
             vKrho[r] = s1;
             vy[r] = vc[n + r] + s2;
         }
-        for (int i = lane; i < n; i += kWave) {
-            float s = 0.0f;
-            for (int j = 0; j < n; ++j) s = fmaf(sAcl[i * LDN + j], vrho[j], s);
-            vv[i] = vwbar[i] + s;
-        }
+        wave_matvec(n, n, [&](int i, int j) { return sAcl[i * LDN + j]; }, [&](int j) { return vrho[j]; },
+                    [&](int i, float s) { vv[i] = vwbar[i] + s; });
         wsync();
         // T2 = Kbar = gK + y rho'  [m][n]
         wave_for_2d(m, n, [&](int i, int j, int idx) {
@@ -270,84 +253,28 @@ __global__ __launch_bounds__(kWave) void ss_vjp_kernel(SsVjpArgs a)
         }
         if (of.p) {
             float *df = of.p + (size_t)b * of.sb;
-            for (int i = lane; i < n; i += kWave) {
-                float s = 0.0f;
-                for (int j = 0; j < n; ++j) s = fmaf(sP[i * LDN + j], vv[j], s);
-                df[i] = s;
-            }
+            wave_matvec(n, n, [&](int i, int j) { return sP[i * LDN + j]; }, [&](int j) { return vv[j]; }, [&](int i, float s) { df[i] = s; });
         }
         if (oc.p) {
             float *dc = oc.p + (size_t)b * oc.sb;
             for (int i = lane; i < d; i += kWave) dc[i] = i < n ? vrho[i] : vKrho[i - n] - vkap[i - n];
         }
     } else {
-        const float qnan = __builtin_nanf("");
         const int sizes[kOuts] = {n * d, n, d * d, d};
         for (int k = 0; k < kOuts; ++k)
-            if (a.o[k].p)
-                for (int i = lane; i < sizes[k]; i += kWave) a.o[k].p[(size_t)b * a.o[k].sb + i] = qnan;
+            if (a.o[k].p) fill_nan(a.o[k].p + (size_t)b * a.o[k].sb, sizes[k]);
     }
     if (lane == 0) a.status[b] = status;
 }
 
-// partial[chunk][e] = sum of rec[b][e] over the chunk's instances, in a fixed order: four interleaved running sums
-// (instances b0 + 4i + q), then ((s0 + s1) + (s2 + s3)).  Grid (chunks, element slices of kRedThreads).
-__global__ void __launch_bounds__(kRedThreads) ss_vjp_reduce_stage1(const float *rec, int B, int nE, float *partial)
-{
-    const int chunk = blockIdx.x;
-    const int e = blockIdx.y * kRedThreads + threadIdx.x;
-    if (e >= nE) return;
-    const int b0 = chunk * kRedChunk, b1 = min(B, b0 + kRedChunk);
-    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    int bb = b0;
-    for (; bb + 4 <= b1; bb += 4)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] += rec[(size_t)(bb + q) * nE + e];
-    for (int q = 0; bb < b1; ++bb, ++q) s[q] += rec[(size_t)bb * nE + e];
-    partial[(size_t)chunk * nE + e] = (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-// out[e] = sum over the chunks of partial[chunk][e]: one block per element, strided partial sums per thread, then a
-// fixed-order tree over the block in LDS
-__global__ void __launch_bounds__(kRedThreads) ss_vjp_reduce_stage2(const float *partial, int chunks, int nE, float *out)
-{
-    __shared__ float t[kRedThreads];
-    const int e = blockIdx.x, tid = threadIdx.x;
-    float s = 0.0f;
-    for (int k = tid; k < chunks; k += kRedThreads) s += partial[(size_t)k * nE + e];
-    t[tid] = s;
-    __syncthreads();
-    for (int w = kRedThreads / 2; w > 0; w >>= 1) {
-        if (tid < w) t[tid] += t[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) out[e] = t[0];
-}
-
 bool fast_supported(int n, int m) { return n <= 16 && m <= 16; }
 
-size_t up64(size_t x) { return (x + 63) / 64 * 64; }
-
-int out_size(int k, int n, int m)
+// the batch sum's workspace layout for the summed ones of dF, df, dC, dc
+BatchSumPlan sum_plan(int B, int n, int m, unsigned summed)
 {
     const int d = n + m;
-    return k == kOutF ? n * d : k == kOutf ? n : k == kOutC ? d * d : d;
-}
-
-// workspace in floats: a record array [B][size] per summed output, then the stage-1 partial sums (reused by each output)
-size_t workspace_floats(int B, int n, int m, unsigned summed, size_t rec_off[kOuts], size_t *partial_off)
-{
-    const size_t chunks = ((size_t)B + kRedChunk - 1) / kRedChunk;
-    size_t o = 0, widest = 0;
-    for (int k = 0; k < kOuts; ++k) {
-        if (!(summed >> k & 1u)) continue;
-        if (rec_off) rec_off[k] = o;
-        o += up64((size_t)B * out_size(k, n, m));
-        widest = widest > (size_t)out_size(k, n, m) ? widest : (size_t)out_size(k, n, m);
-    }
-    if (!summed) return 0;
-    if (partial_off) *partial_off = o;
-    return o + up64(chunks * widest);
+    const int sizes[kOuts] = {n * d, n, d * d, d}, slots[kOuts] = {1, 1, 1, 1};
+    return batch_sum_plan(B, kRedChunk, kOuts, sizes, slots, summed);
 }
 
 }  // namespace
@@ -361,7 +288,7 @@ extern "C" {
 size_t tfmpc_lqr_steady_state_vjp_workspace_bytes(int B, int n, int m)
 {
     if (B <= 1 || n <= 0 || m <= 0 || n > 32 || m > 32) return 0;
-    return workspace_floats(B, n, m, (1u << kOuts) - 1, nullptr, nullptr) * sizeof(float);
+    return sum_plan(B, n, m, (1u << kOuts) - 1).floats * sizeof(float);
 }
 
 const char *tfmpc_lqr_steady_state_vjp_kernel_name(int n, int m)
@@ -393,9 +320,9 @@ int tfmpc_lqr_steady_state_vjp_f32(int B, int n, int m,
     unsigned summed = 0;
     for (int q = 0; q < kOuts; ++q)
         if (outs[q] && strides[q] == 0 && B > 1) summed |= 1u << q;
-    size_t rec_off[kOuts] = {}, partial_off = 0;
-    const size_t need = workspace_floats(B, n, m, summed, rec_off, &partial_off);
-    if (need && (!workspace || workspace_bytes < need * sizeof(float))) return TFMPC_ERR_WORKSPACE;
+    const BatchSumPlan plan = sum_plan(B, n, m, summed);
+    if (!plan.fits) return TFMPC_ERR_UNSUPPORTED;
+    if (plan.floats && (!workspace || workspace_bytes < plan.floats * sizeof(float))) return TFMPC_ERR_WORKSPACE;
     float *w = static_cast<float *>(workspace);
 
     SsVjpArgs a{};
@@ -407,7 +334,7 @@ int tfmpc_lqr_steady_state_vjp_f32(int B, int n, int m,
     a.K = K; a.k = k; a.P = P; a.p = p; a.fwd_status = fwd_status;
     a.gK = gK; a.gk = gk; a.gP = gP; a.gp = gp;
     for (int q = 0; q < kOuts; ++q) {
-        if (summed >> q & 1u) a.o[q] = {w + rec_off[q], (long)out_size(q, n, m)};
+        if (summed >> q & 1u) a.o[q] = {w + plan.rec_off[q], (long)plan.size[q]};
         else a.o[q] = {outs[q], strides[q]};
     }
     a.status = status;
@@ -415,17 +342,7 @@ int tfmpc_lqr_steady_state_vjp_f32(int B, int n, int m,
     if (fast_supported(n, m)) hipLaunchKernelGGL(ss_vjp_kernel<16>, dim3(B), dim3(kWave), 0, s, a);
     else hipLaunchKernelGGL(ss_vjp_kernel<32>, dim3(B), dim3(kWave), 0, s, a);
     if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-    const int chunks = (B + kRedChunk - 1) / kRedChunk;
-    for (int q = 0; q < kOuts; ++q) {
-        if (!(summed >> q & 1u)) continue;
-        const int nE = out_size(q, n, m);
-        hipLaunchKernelGGL(ss_vjp_reduce_stage1, dim3(chunks, (nE + kRedThreads - 1) / kRedThreads), dim3(kRedThreads), 0, s,
-                           w + rec_off[q], B, nE, w + partial_off);
-        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-        hipLaunchKernelGGL(ss_vjp_reduce_stage2, dim3(nE), dim3(kRedThreads), 0, s, w + partial_off, chunks, nE, outs[q]);
-        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-    }
-    return TFMPC_OK;
+    return batch_sum_run<kRedChunk, kSumTree>(plan, w, outs, strides, s);
 }
 
 }  // extern "C"

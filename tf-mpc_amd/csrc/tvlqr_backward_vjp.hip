@@ -17,14 +17,15 @@
 // Layout as lqr_steady_state_vjp.hip: every matrix of the step in the wave's LDS slice, every product on
 // v_mfma_f32_16x16x4_f32 (wave_ops.h mfma_matmul, strict fp32).  NP = 16 serves n <= 16, NP = 32 serves n <= 32, both with
 // m <= 16.  A gradient whose time stride is 0 is accumulated in the output in time order (a lane owns the same elements at
-// every step); one whose batch stride is 0 is written as per-instance records into the workspace and summed by
-// bvjp_reduce_stage1 (fixed-order sums over chunks of instances) and bvjp_reduce_stage2 (fixed-order sum of the chunks).
-// No atomics: the same call gives the same bits.  A flagged instance (forward or here) gets NaN in its own rows.
+// every step); one whose batch stride is 0 is written as per-instance records into the workspace and summed by the shared
+// batch sum (batch_sum.h: chunks of 256 instances, then the chunks in order).  A flagged instance (forward or here) gets NaN
+// in its own rows.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/tfmpc_hip.h"
+#include "batch_sum.h"
 #include "tvlqr_kernels.h"
 #include "wave_ops.h"
 
@@ -33,8 +34,7 @@ namespace tfmpc {
 namespace {
 
 constexpr int kMP = 16;                // controls per tile: m <= 16
-constexpr int kRedChunk = 256;         // instances per stage-1 block
-constexpr int kRedThreads = 256;
+constexpr int kRedChunk = 256;         // instances per stage-1 block of the batch sum
 enum { kOutF, kOutf, kOutC, kOutc, kOutCf, kOutcf, kOuts };
 
 struct BvOut {
@@ -125,23 +125,14 @@ __global__ __launch_bounds__(kWave) void tvb_vjp_kernel(BvArgs a)
                          zero, [&](int i, int j, float x) { sPF[i * LDD + j] = x; });
         wave_matmul_mfma(m, n, n, [&](int i, int kk) { return sK[i * LDN + kk]; }, [&](int kk, int j) { return sVb[kk * LDN + j]; },
                          zero, [&](int i, int j, float x) { sKV[i * LDN + j] = x; });
-        for (int i = lane; i < n; i += kWave) {
-            float s = 0.0f;
-            for (int j = 0; j < n; ++j) s = fmaf(sP[i * LDN + j], vf[j], s);
-            vr[i] = s + vs[i];
-        }
+        wave_matvec(n, n, [&](int i, int j) { return sP[i * LDN + j]; }, [&](int j) { return vf[j]; },
+                    [&](int i, float s) { vr[i] = s + vs[i]; });
         lds_sync();
         // Quu = C_uu + F_u' (P F)_u, symmetrised as in the forward
         wave_matmul_mfma(m, m, n, [&](int i, int kk) { return sF[kk * LDD + n + i]; }, [&](int kk, int j) { return sPF[kk * LDD + n + j]; },
                          [&](int i, int j) { return Cg[(n + i) * d + n + j]; }, [&](int i, int j, float x) { aug[i * LDA + j] = x; });
         wsync();
-        wave_for_2d(m, m, [&](int i, int j, int) {
-            if (i < j) {
-                const float s = 0.5f * (aug[i * LDA + j] + aug[j * LDA + i]);
-                aug[i * LDA + j] = s;
-                aug[j * LDA + i] = s;
-            }
-        });
+        symmetrise(aug, LDA, m);
         wsync();
         if (wave_gauss_jordan<false>(aug, LDA, m, m + n + 1, fac, fac)) {
             status |= TFMPC_ST_NOT_PD;
@@ -150,11 +141,8 @@ __global__ __launch_bounds__(kWave) void tvb_vjp_kernel(BvArgs a)
         // G = KV + Kt [m][n];  qbar = [vbar; kt + K vbar + abar k]
         wave_for_2d(m, n, [&](int r, int j, int) { sG[r * LDN + j] = sKV[r * LDN + j] - aug[r * LDA + m + j]; });
         for (int i = lane; i < n; i += kWave) vq[i] = vvb[i];
-        for (int r = lane; r < m; r += kWave) {
-            float s = 0.0f;
-            for (int j = 0; j < n; ++j) s = fmaf(sK[r * LDN + j], vvb[j], s);
-            vq[n + r] = fmaf(abar, vk[r], s - aug[r * LDA + m + n]);
-        }
+        wave_matvec(m, n, [&](int r, int j) { return sK[r * LDN + j]; }, [&](int j) { return vvb[j]; },
+                    [&](int r, float s) { vq[n + r] = fmaf(abar, vk[r], s - aug[r * LDA + m + n]); });
         lds_sync();
         // Qbar: the uu block (symmetrised below), xx = Vbar, ux / xu;  rbar = F qbar
         wave_matmul_mfma(m, m, n, [&](int i, int kk) { return sG[i * LDN + kk]; }, [&](int kk, int j) { return sK[j * LDN + kk]; },
@@ -166,19 +154,9 @@ __global__ __launch_bounds__(kWave) void tvb_vjp_kernel(BvArgs a)
             sQb[(n + r) * LDD + i] = x;
             sQb[i * LDD + n + r] = x;
         });
-        for (int i = lane; i < n; i += kWave) {
-            float s = 0.0f;
-            for (int j = 0; j < d; ++j) s = fmaf(sF[i * LDD + j], vq[j], s);
-            vrb[i] = s;
-        }
+        wave_matvec(n, d, [&](int i, int j) { return sF[i * LDD + j]; }, [&](int j) { return vq[j]; }, [&](int i, float s) { vrb[i] = s; });
         lds_sync();
-        wave_for_2d(m, m, [&](int i, int j, int) {
-            if (i < j) {
-                const float s = 0.5f * (sQb[(n + i) * LDD + n + j] + sQb[(n + j) * LDD + n + i]);
-                sQb[(n + i) * LDD + n + j] = s;
-                sQb[(n + j) * LDD + n + i] = s;
-            }
-        });
+        symmetrise(sQb + n * LDD + n, LDD, m);
         lds_sync();
         // dF = 2 (PF) Qbar + r qbar';  T = F Qbar [n][d];  df = P rbar + abar r
         if (oF.p)
@@ -188,11 +166,8 @@ __global__ __launch_bounds__(kWave) void tvb_vjp_kernel(BvArgs a)
         wave_matmul_mfma(n, d, d, [&](int i, int kk) { return sF[i * LDD + kk]; }, [&](int kk, int j) { return sQb[kk * LDD + j]; },
                          zero, [&](int i, int j, float x) { sT[i * LDD + j] = x; });
         if (of.p)
-            for (int i = lane; i < n; i += kWave) {
-                float s = 0.0f;
-                for (int j = 0; j < n; ++j) s = fmaf(sP[i * LDN + j], vrb[j], s);
-                emit(of, b, t, i, fmaf(abar, vr[i], s));
-            }
+            wave_matvec(n, n, [&](int i, int j) { return sP[i * LDN + j]; }, [&](int j) { return vrb[j]; },
+                        [&](int i, float s) { emit(of, b, t, i, fmaf(abar, vr[i], s)); });
         lds_sync();
         // Vbar <- sym(T F' + rbar f' + abar f f' / 2) (through PF's tile), vbar <- rbar + abar f
         wave_matmul_mfma(n, n, d, [&](int i, int kk) { return sT[i * LDD + kk]; }, [&](int kk, int j) { return sF[j * LDD + kk]; },
@@ -222,73 +197,24 @@ __global__ __launch_bounds__(kWave) void tvb_vjp_kernel(BvArgs a)
         if (ocf.p)
             for (int i = lane; i < n; i += kWave) ocf.p[(size_t)b * ocf.sb + i] = vvb[i];
     } else {
-        const float qnan = __builtin_nanf("");
         for (int q = 0; q < kOuts; ++q) {
             const BvOut &o = a.o[q];
             if (!o.p) continue;
             const int slots = (q < kOutCf && o.st) ? T : 1;
-            for (int t = 0; t < slots; ++t)
-                for (int e = lane; e < sizes[q]; e += kWave) o.p[(size_t)b * o.sb + (size_t)t * o.st + e] = qnan;
+            for (int t = 0; t < slots; ++t) fill_nan(o.p + (size_t)b * o.sb + (size_t)t * o.st, sizes[q]);
         }
     }
     if (lane == 0) a.status[b] = status;
 }
 
-// partial[chunk][e] = sum of rec[b][e] over the chunk's instances, in a fixed order: four interleaved running sums
-// (instances b0 + 4i + q), then ((s0 + s1) + (s2 + s3)).  Grid (element slices of kRedThreads, chunks).
-__global__ void __launch_bounds__(kRedThreads) bvjp_reduce_stage1(const float *rec, int B, size_t nE, float *partial)
-{
-    const int chunk = blockIdx.y;
-    const size_t e = (size_t)blockIdx.x * kRedThreads + threadIdx.x;
-    if (e >= nE) return;
-    const int b0 = chunk * kRedChunk, b1 = min(B, b0 + kRedChunk);
-    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    int bb = b0;
-    for (; bb + 4 <= b1; bb += 4)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] += rec[(size_t)(bb + q) * nE + e];
-    for (int q = 0; bb < b1; ++bb, ++q) s[q] += rec[(size_t)bb * nE + e];
-    partial[(size_t)chunk * nE + e] = (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-// out[slot * st + e'] = sum over the chunks, in order, of partial[chunk][slot * size + e']
-__global__ void __launch_bounds__(kRedThreads) bvjp_reduce_stage2(const float *partial, int chunks, size_t nE, int size, float *out,
-                                                                  long st)
-{
-    const size_t e = (size_t)blockIdx.x * kRedThreads + threadIdx.x;
-    if (e >= nE) return;
-    float s = 0.0f;
-    for (int k = 0; k < chunks; ++k) s += partial[(size_t)k * nE + e];
-    out[(e / size) * (size_t)st + e % size] = s;
-}
-
 bool shape_supported(int n, int m) { return n <= 32 && m <= kMP; }
 
-size_t up64(size_t x) { return (x + 63) / 64 * 64; }
-
-int out_size(int q, int n, int m)
+// the batch sum's workspace layout for the summed ones of dF, df, dC, dc (slots[q] = T or 1) and dCfin, dcfin
+BatchSumPlan sum_plan(int B, int n, int m, const int slots[kOuts], unsigned summed)
 {
     const int d = n + m;
     const int sizes[kOuts] = {n * d, n, d * d, d, n * n, n};
-    return sizes[q];
-}
-
-// Workspace in floats: a record array [B][slots][size] per summed output (slots[q] = T or 1), then the stage-1 partial
-// sums (reused by each output).
-size_t workspace_floats(int B, int n, int m, const int slots[kOuts], unsigned summed, size_t rec_off[kOuts], size_t *partial_off)
-{
-    const size_t chunks = ((size_t)B + kRedChunk - 1) / kRedChunk;
-    size_t o = 0, widest = 0;
-    for (int q = 0; q < kOuts; ++q) {
-        if (!(summed >> q & 1u)) continue;
-        const size_t nE = (size_t)slots[q] * out_size(q, n, m);
-        if (rec_off) rec_off[q] = o;
-        o += up64((size_t)B * nE);
-        widest = widest > nE ? widest : nE;
-    }
-    if (!summed) return 0;
-    if (partial_off) *partial_off = o;
-    return o + up64(chunks * widest);
+    return batch_sum_plan(B, kRedChunk, kOuts, sizes, slots, summed);
 }
 
 }  // namespace
@@ -303,7 +229,7 @@ size_t tfmpc_tvlqr_backward_vjp_workspace_bytes(int B, int n, int m, int T)
 {
     if (B <= 1 || n <= 0 || m <= 0 || T <= 0 || !shape_supported(n, m)) return 0;
     const int slots[kOuts] = {T, T, T, T, 1, 1};
-    return workspace_floats(B, n, m, slots, (1u << kOuts) - 1, nullptr, nullptr) * sizeof(float);
+    return sum_plan(B, n, m, slots, (1u << kOuts) - 1).floats * sizeof(float);
 }
 
 const char *tfmpc_tvlqr_backward_vjp_kernel_name(int n, int m, int T)
@@ -334,8 +260,6 @@ int tfmpc_tvlqr_backward_vjp_f32(int B, int n, int m, int T,
     for (long s : {sF_b, sF_t, sf_b, sf_t, sC_b, sC_t, sc_b, sc_t, sCfin_b, scfin_b, sdF_b, sdF_t, sdf_b, sdf_t, sdC_b, sdC_t,
                    sdc_b, sdc_t, sdCfin_b, sdcfin_b})
         if (s < 0) return TFMPC_ERR_ARG;
-    const int chunks = (B + kRedChunk - 1) / kRedChunk;
-    if (chunks > 65535) return TFMPC_ERR_UNSUPPORTED;              // the reduction's chunks are one grid axis
     float *outs[kOuts] = {dF, df, dC, dc, dCfin, dcfin};
     const long sb[kOuts] = {sdF_b, sdf_b, sdC_b, sdc_b, sdCfin_b, sdcfin_b};
     const long st[kOuts] = {sdF_t, sdf_t, sdC_t, sdc_t, 0, 0};
@@ -346,9 +270,9 @@ int tfmpc_tvlqr_backward_vjp_f32(int B, int n, int m, int T,
         slots[q] = st[q] ? T : 1;
         if (outs[q] && sb[q] == 0 && B > 1) summed |= 1u << q;
     }
-    size_t rec_off[kOuts] = {}, partial_off = 0;
-    const size_t need = workspace_floats(B, n, m, slots, summed, rec_off, &partial_off);
-    if (need && (!workspace || workspace_bytes < need * sizeof(float))) return TFMPC_ERR_WORKSPACE;
+    const BatchSumPlan plan = sum_plan(B, n, m, slots, summed);
+    if (!plan.fits) return TFMPC_ERR_UNSUPPORTED;                  // the batch sum's blocks are one grid axis
+    if (plan.floats && (!workspace || workspace_bytes < plan.floats * sizeof(float))) return TFMPC_ERR_WORKSPACE;
     float *w = static_cast<float *>(workspace);
 
     BvArgs a{};
@@ -359,8 +283,8 @@ int tfmpc_tvlqr_backward_vjp_f32(int B, int n, int m, int T,
     a.K = K; a.k = k; a.V = V; a.v = v; a.fwd_status = fwd_status;
     a.gK = gK; a.gk = gk; a.gV = gV; a.gv = gv; a.gconst = gconst;
     for (int q = 0; q < kOuts; ++q) {
-        const long size = out_size(q, n, m);
-        if (summed >> q & 1u) a.o[q] = {w + rec_off[q], (long)slots[q] * size, st[q] ? size : 0};
+        const long size = plan.size[q];
+        if (summed >> q & 1u) a.o[q] = {w + plan.rec_off[q], (long)slots[q] * size, st[q] ? size : 0};
         else a.o[q] = {outs[q], sb[q], st[q]};
     }
     a.status = status;
@@ -368,17 +292,7 @@ int tfmpc_tvlqr_backward_vjp_f32(int B, int n, int m, int T,
     if (n <= 16) hipLaunchKernelGGL(tvb_vjp_kernel<16>, dim3(B), dim3(kWave), 0, s, a);
     else hipLaunchKernelGGL(tvb_vjp_kernel<32>, dim3(B), dim3(kWave), 0, s, a);
     if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-    for (int q = 0; q < kOuts; ++q) {
-        if (!(summed >> q & 1u)) continue;
-        const int size = out_size(q, n, m);
-        const size_t nE = (size_t)slots[q] * size;
-        const unsigned slices = (unsigned)((nE + kRedThreads - 1) / kRedThreads);
-        hipLaunchKernelGGL(bvjp_reduce_stage1, dim3(slices, chunks), dim3(kRedThreads), 0, s, w + rec_off[q], B, nE, w + partial_off);
-        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-        hipLaunchKernelGGL(bvjp_reduce_stage2, dim3(slices), dim3(kRedThreads), 0, s, w + partial_off, chunks, nE, size, outs[q], st[q]);
-        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-    }
-    return TFMPC_OK;
+    return batch_sum_run<kRedChunk, kSumInOrder>(plan, w, outs, st, s);
 }
 
 }  // extern "C"

@@ -15,7 +15,8 @@
 //                         all four partial sums -- GEMMs over instances on v_mfma_f32_16x16x4_f32 for n <= 16, d <= 32
 //                         (vjp_reduce_steps_mfma16), LDS-tiled scalar sums otherwise (vjp_reduce_steps) -- then a
 //                         fixed-order sum over chunks per output (vjp_reduce_steps_stage2).  dCfin, dcfin, dx0: one
-//                         record per instance, vjp_reduce_stage1 / stage2.  No atomics: the same call gives the same bits.
+//                         record per instance, vjp_reduce_stage1, then the chunks in order (batch_sum.h).  No atomics: the
+//                         same call gives the same bits.
 // An instance whose adjoint solve reports TFMPC_ST_NOT_PD or TFMPC_ST_SINGULAR contributes NaN (its own rows, and
 // any reduction that includes it).  fp32 throughout; no scratch memory.
 //
@@ -30,6 +31,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "batch_sum.h"
 #include "lqr_kernels.h"
 #include "tvlqr_kernels.h"
 
@@ -427,16 +429,6 @@ __global__ void __launch_bounds__(kRedThreads) vjp_reduce_stage1(VjpArgs a, int 
             if (e < nE) partial[((size_t)chunk * slots + slot) * nE + e] = acc[q];
         }
     }
-}
-
-__global__ void vjp_reduce_stage2(const float *partial, int chunks, int slots, int nE, float *out, long st)
-{
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)slots * nE) return;
-    const int slot = (int)(idx / nE), e = (int)(idx % nE);
-    float s = 0.0f;
-    for (int k = 0; k < chunks; ++k) s += partial[((size_t)k * slots + slot) * nE + e];
-    out[(size_t)slot * st + e] = s;
 }
 
 // Fused per-step reductions: ONE pass over the records emits every requested batch-shared per-step gradient (dF, df,
@@ -863,8 +855,8 @@ int vjp_impl(TFMPC_VJP_PARAMS_HEAD, TFMPC_VJP_PARAMS_TAIL, int32_t *status, void
         hipLaunchKernelGGL(vjp_reduce_stage1, dim3(chunks, 1), dim3(kRedThreads), (size_t)kTile * W * sizeof(float), s,
                            sw, k, nEs[k], 1, partial);
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-        hipLaunchKernelGGL(vjp_reduce_stage2, dim3((unsigned)((nEs[k] + 255) / 256)), dim3(256), 0, s, partial, chunks,
-                           1, nEs[k], o.p, 0L);
+        hipLaunchKernelGGL(batch_sum_stage2_in_order<kRedThreads>, dim3((unsigned)((nEs[k] + 255) / 256)), dim3(kRedThreads), 0, s,
+                           partial, chunks, (size_t)nEs[k], nEs[k], o.p, 0L);      // the chunks in order (batch_sum.h)
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
     }
     if (box) {                       // bound gradients shared by the batch: the sweep's records, chunks, then steps

@@ -9,6 +9,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
+
 namespace tfmpc {
 
 constexpr int kWave = 64;
@@ -208,6 +210,38 @@ __device__ __forceinline__ void wave_for_2d(int rows, int cols, F f)
         if (j >= cols) { j -= cols; ++i; }
         f(i, j, idx);
     }
+}
+
+// X <- (X + X') / 2 in place, X an n x n block with leading dimension ld; the pair (i, j), (j, i) belongs to one lane
+__device__ __forceinline__ void symmetrise(float *X, int ld, int n)
+{
+    wave_for_2d(n, n, [&](int i, int j, int) {
+        if (i < j) {
+            const float s = 0.5f * (X[i * ld + j] + X[j * ld + i]);
+            X[i * ld + j] = s;
+            X[j * ld + i] = s;
+        }
+    });
+}
+
+// out(i, sum_k a(i, k) x(k)), i < rows, a row per lane: s = 0, then s = fmaf(a(i, k), x(k), s) for k = 0 .. K - 1
+template <class FA, class FX, class FOut>
+__device__ __forceinline__ void wave_matvec(int rows, int K, FA a, FX x, FOut out)
+{
+    for (int i = lane_id(); i < rows; i += kWave) {
+        float s = 0.0f;
+        for (int k = 0; k < K; ++k) s = fmaf(a(i, k), x(k), s);
+        out(i, s);
+    }
+}
+
+__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= FLT_MAX; }
+
+// quiet NaN into p[0 .. count): the outputs of a flagged instance
+__device__ __forceinline__ void fill_nan(float *p, int count)
+{
+    const float qnan = __builtin_nanf("");
+    for (int i = lane_id(); i < count; i += kWave) p[i] = qnan;
 }
 
 // Global -> LDS copy of a row-major [rows][cols] matrix into leading dimension ld.

@@ -30,11 +30,6 @@ def graph_operands(lqr):
     return F, _as_column(f, n), C, _as_column(c, d)
 
 
-def _stride(g, Bk):
-    """Batch stride of a contiguous gradient buffer: 0 (summed over the batch) for an operand without a batch axis."""
-    return g[0].numel() if g.dim() == 3 and Bk > 0 else 0
-
-
 class SteadyStateFunction(torch.autograd.Function):
 
     @staticmethod
@@ -54,12 +49,11 @@ class SteadyStateFunction(torch.autograd.Function):
         lib = _hip.require_gpu()
         Bk, m, n = K.shape
         dev = K.device
-        alloc = torch.zeros if Bk == 0 else torch.empty
-        grads = [alloc(shape, device=dev) if ctx.needs_input_grad[3 + i] else None for i, shape in enumerate(ctx.shapes)]
+        grads = tvlqr_grad.alloc_grads(ctx.shapes, ctx.needs_input_grad[3:], Bk, dev)
         out_args = []
         summed = False
         for g in grads:
-            stride = _stride(g, Bk) if g is not None else 0
+            stride = tvlqr_grad.grad_strides(g, 3, False)[0]      # 0 (summed over the batch) for an operand without a batch axis
             summed |= g is not None and stride == 0 and Bk > 1
             out_args += [_hip.ptr(g), stride]
         ups = [None if g is None else g.to(torch.float32).contiguous() for g in (gK, gk, gP, gp)]

@@ -42,15 +42,13 @@ class BackwardFunction(torch.autograd.Function):
         lib = _hip.require_gpu()
         Bk, T, m, n = K.shape
         dev = K.device
-        need, shapes = ctx.needs_input_grad, ctx.shapes
         nd_model = 4 if problem.timed else 3
-        alloc = torch.zeros if Bk == 0 else torch.empty
-        grads = [alloc(shapes[i], device=dev) if need[i + 1] and shapes[i] is not None else None for i in range(6)]
+        grads = tvlqr_grad.alloc_grads(ctx.shapes, ctx.needs_input_grad[1:], Bk, dev)
         args = []
         for g in grads[:4]:
-            args += [_hip.ptr(g), *(tvlqr_grad._strides(g, nd_model, problem.timed) if g is not None else (0, 0))]
+            args += [_hip.ptr(g), *tvlqr_grad.grad_strides(g, nd_model, problem.timed)]
         for g in grads[4:]:
-            args += [_hip.ptr(g), tvlqr_grad._strides(g, 3, False)[0] if g is not None else 0]
+            args += [_hip.ptr(g), tvlqr_grad.grad_strides(g, 3, False)[0]]
         ups = [None if g is None else g.to(torch.float32).contiguous() for g in (gK, gk, gV, gv, gconst)]
         status = torch.zeros((Bk,), dtype=torch.int32, device=dev)
         ws_bytes = int(lib.tfmpc_tvlqr_backward_vjp_workspace_bytes(Bk, n, m, T))

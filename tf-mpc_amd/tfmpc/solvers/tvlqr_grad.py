@@ -42,14 +42,24 @@ class Problem:
         self.run, self.model, self.timed, self.owner = run, model, timed, owner
 
 
-def _strides(g, ndim_batched, timed):
-    """(batch stride, time stride) of a contiguous gradient buffer ``g``; 0 = summed over that axis."""
+def grad_strides(g, ndim_batched, timed):
+    """(batch stride, time stride) of a contiguous gradient buffer ``g`` (``None``: no gradient, (0, 0)); 0 = summed over
+    that axis."""
+    if g is None:
+        return 0, 0
     batched = g.dim() == ndim_batched
     sb = g[0].numel() if batched and g.shape[0] > 0 else 0
     st = 0
     if timed and g.shape[-3] > 1:
         st = g.shape[-2] * g.shape[-1]
     return sb, st
+
+
+def alloc_grads(shapes, needed, Bk, device):
+    """One fp32 buffer per operand shape whose gradient is needed, else ``None`` (also for an absent operand, shape
+    ``None``).  Zeros over an empty batch, where no kernel writes."""
+    alloc = torch.zeros if Bk == 0 else torch.empty
+    return [alloc(shape, device=device) if need and shape is not None else None for shape, need in zip(shapes, needed)]
 
 
 class SolveFunction(torch.autograd.Function):
@@ -73,17 +83,13 @@ class SolveFunction(torch.autograd.Function):
         Bk, T1, n = states.shape[0], states.shape[1], states.shape[2]
         T, m = T1 - 1, actions.shape[2]
         dev = states.device
-        need = ctx.needs_input_grad
-        shapes = ctx.meta
         nd_model = 4 if problem.timed else 3
-        alloc = torch.zeros if Bk == 0 else torch.empty
-        grads = [alloc(shapes[i], device=dev) if need[i + 1] and shapes[i] is not None else None for i in range(7)]
-        gx0, gF, gf, gC, gc, gCf, gcf = grads
+        gx0, gF, gf, gC, gc, gCf, gcf = alloc_grads(ctx.meta, ctx.needs_input_grad[1:], Bk, dev)
         args = []
         for g in (gF, gf, gC, gc):
-            args += [_hip.ptr(g), *(_strides(g, nd_model, problem.timed) if g is not None else (0, 0))]
+            args += [_hip.ptr(g), *grad_strides(g, nd_model, problem.timed)]
         for g in (gCf, gcf, gx0):
-            args += [_hip.ptr(g), _strides(g, 3, False)[0] if g is not None else 0]
+            args += [_hip.ptr(g), grad_strides(g, 3, False)[0]]
         ups = [None if g is None else g.to(torch.float32).contiguous() for g in (g_states, g_actions, g_costs)]
         status = torch.zeros((Bk,), dtype=torch.int32, device=dev)
         ws_bytes = int(lib.tfmpc_tvlqr_vjp_workspace_bytes(Bk, n, m, T))
