@@ -45,6 +45,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "lqr_kernels.h"
 #include "options.h"
@@ -194,11 +195,14 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
         const int g1_src = (i == M) ? kKs + (N + M) * 8 + q : kZero + q;
         __syncthreads();
 
-        for (int t = T - 1; t >= 0; --t) {
+        // One sweep step.  LAST (a std::bool_constant) marks the step t == 0 of a launch without value outputs, peeled below: nothing reads
+        // its V', v', so it ends at its gains.
+        auto sweep_step = [&](const int t, auto LAST) __attribute__((always_inline)) {
             // 1. W = V F~ (+ v on column 24)                                  lqr.py:74,77-78
-            f32x4 W0 = {0.f, 0.f, 0.f, 0.f}, W1 = {0.f, 0.f, 0.f, 0.f};
+            //    v enters W_1 as the accumulator of its product (vd is zero outside lanes i == 8, see step 4): no add
+            f32x4 W0 = {0.f, 0.f, 0.f, 0.f}, W1 = vd;
             if (BF3) {
-                const VarFrag Vf = var_frag(Vd);
+                const VarFrag Vf = var_frag_block(Vd);
                 W0 = mm_var_const(Vf, Fc0, W0);
                 W1 = mm_var_const(Vf, Fc1, W1);
             } else {
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
                 }
             }
             float fw = 0.0f, fv = 0.0f;
-            if (VALUE) {     // f^T (V f) and f^T v for the const recursion (lqr.py:120)
+            if (VALUE) {     // f^T (V f + v) and f^T v for the const recursion (lqr.py:120); W_1 itself is what every instantiation computes
                 float pw = 0.0f, pv = 0.0f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -219,14 +223,13 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
                 fw = wave_sum(i == M ? pw : 0.0f);
                 fv = wave_sum(i == M ? pv : 0.0f);
             }
-            W1 += vd;                            // vd is zero outside lanes i == 8 (see step 4)
             // 2. Q~ = C~ + F~^T W                                              lqr.py:75-78
             // Three tiles: Q_xx = F_x^T W_0; [Q_uu | q_u] = F~_1^T W_1; and W_1^T F_x, whose rows
             // 0..7 are Q_ux (= F_u^T V F_x: V is kept exactly symmetric, step 4, so this equals the
             // F~_1^T W_0 tile that is no longer computed) and whose row 8 is q_x^T = (V f + v)^T F_x.
             f32x4 T00 = Cd00, T01t = Cd01t, T11 = Cd11;
             if (BF3) {
-                const VarFrag W0f = var_frag(W0), W1f = var_frag(W1);
+                const VarFrag W0f = var_frag_block(W0), W1f = var_frag_block(W1);
                 T00 = mm_const_var(Fc0, W0f, T00);
                 T01t = mm_var_const(W1f, Fc0, T01t);
                 T11 = mm_const_var(Fc1, W1f, T11);
@@ -281,27 +284,33 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
             //    contraction over the 8 actions as 2 k-steps: a = 4s + q
             //    vacc accumulates v' on q_x in column 24 (lanes i == 8); every other lane reads its
             //    operands from the always-zero pad columns, so the next v is 0 there.
-            f32x4 vacc = *reinterpret_cast<const f32x4 *>(&lds[t01_src]);
+            if constexpr (!decltype(LAST)::value) {
+                f32x4 vacc = *reinterpret_cast<const f32x4 *>(&lds[t01_src]);
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const float ax = lds[kMs + i * 8 + 4 * s2 + q];            // Q_xu[i][4s+q] = Q_ux[4s+q][i]
-                const float g0 = lds[kKs + i * 8 + 4 * s2 + q];            // K[4s+q][i]
-                const float g1 = lds[g1_src + 4 * s2];                     // K~[4s+q][24] in lanes i == 8
-                T00 = mfma(ax, g0, T00);
-                vacc = mfma(ax, g1, vacc);
-            }
-            // V' <- (V' + V'^T) / 2 (transpose through LDS).  The elimination above reads only the
-            // upper triangle of Q_uu; that is consistent only while V carries no antisymmetric part
-            // (otherwise the part it ignores, F_u^T a F_u, is missing from the closed-loop product
-            // and the rounding-level asymmetry of V grows like |F_u K|^2 per step).
-            {
-                float *vt = &lds[kZs];                    // rollout buffer, idle during the sweep
-                *reinterpret_cast<f32x4 *>(&vt[i * kVtLd + 4 * q]) = T00;
-                lds_sync();
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const float ax = lds[kMs + i * 8 + 4 * s2 + q];            // Q_xu[i][4s+q] = Q_ux[4s+q][i]
+                    const float g0 = lds[kKs + i * 8 + 4 * s2 + q];            // K[4s+q][i]
+                    const float g1 = lds[g1_src + 4 * s2];                     // K~[4s+q][24] in lanes i == 8
+                    T00 = mfma(ax, g0, T00);
+                    vacc = mfma(ax, g1, vacc);
+                }
+                // V' <- (V' + V'^T) / 2 (transpose through LDS).  The elimination above reads only the
+                // upper triangle of Q_uu; that is consistent only while V carries no antisymmetric part
+                // (otherwise the part it ignores, F_u^T a F_u, is missing from the closed-loop product
+                // and the rounding-level asymmetry of V grows like |F_u K|^2 per step).
+                // Stored element by element as [row 4q+r][column i] (conflict-free: 80 q + i covers the 64 banks once) and read back as ONE
+                // 16-byte row segment [row i][4q .. 4q+3] = V'^T, which lands in a register quad that pairs with T00 for the packed adds.
+                {
+                    float *vt = &lds[kZs];                    // rollout buffer, idle during the sweep
 #pragma unroll
-                for (int r = 0; r < 4; ++r) Vd[r] = 0.5f * (T00[r] + vt[(4 * q + r) * kVtLd + i]);
+                    for (int r = 0; r < 4; ++r) vt[(4 * q + r) * kVtLd + i] = T00[r];
+                    lds_sync();
+                    const f32x4 Tt = *reinterpret_cast<const f32x4 *>(&vt[i * kVtLd + 4 * q]);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) Vd[r] = 0.5f * (T00[r] + Tt[r]);
+                }
+                vd = vacc;
             }
-            vd = vacc;
             // gains to HBM, row-major K[t][a][j], k[t][a] (the public layout)
             {
                 const int ka = lane >> 3, jc = lane & 7;
@@ -325,8 +334,8 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
             }
             if (VALUE) {
                 // const += 1/2 k^T Q_uu k + k^T q_u + 1/2 f^T V f + f^T v with Q_uu k = -q_u
-                // (lqr.py:113-121); f^T(V f) and f^T v were taken before v entered W.
-                cst += 0.5f * quk + 0.5f * fw + fv;
+                // (lqr.py:113-121); fw = f^T (V f + v) carries one f^T v already: 1/2 f^T V f + f^T v = 1/2 (fw + f^T v).
+                cst += 0.5f * quk + 0.5f * (fw + fv);
                 if (a.V) {
                     float *Vo = a.V + ((size_t)b * T + t) * (n * n);
 #pragma unroll
@@ -355,7 +364,10 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
                 if (OUT16 && a.cst16 && lane == 0) a.cst16[(size_t)b * T + t] = lqr_to_bf16(cst);
             }
             lds_sync();
-        }
+        };
+        constexpr int kPeeled = VALUE ? 0 : 1;       // the VALUE instantiations store V', v' of every step
+        for (int t = T - 1; t >= kPeeled; --t) sweep_step(t, std::false_type{});
+        if (kPeeled && T > 0) sweep_step(0, std::true_type{});
         if (min_pivot_bits <= 0) status |= (min_pivot_bits == 0) ? TFMPC_ST_SINGULAR : TFMPC_ST_NOT_PD;
         if (VALUE && !(cst == cst)) status |= TFMPC_ST_NAN;
     }

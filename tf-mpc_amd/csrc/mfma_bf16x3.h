@@ -64,6 +64,16 @@ __device__ __forceinline__ VarFrag var_frag(f32x4 x)
     const Split3 s = split3(x);
     return VarFrag{u32x6{s.l01, s.l23, s.h01, s.h23, s.m01, s.m23}};
 }
+// The same fragment, pinned as ONE 6-register value (an empty asm that takes and returns the block).  Built from six separate
+// registers the two windows become two 4-register tuples, and the compiler copies h01, h23 into the second one: two v_mov_b32 per
+// fragment.  Through the pin the windows are sub-registers of the block and the copies go (lqr_mfma16x8.hip: 6 per sweep step).
+// Same values; a caller that adopts it should look at its own register count first.
+__device__ __forceinline__ VarFrag var_frag_block(f32x4 x)
+{
+    VarFrag f = var_frag(x);
+    asm("" : "+v"(f.r));
+    return f;
+}
 __device__ __forceinline__ f32x4 mfma_bf(u32x4 a, u32x4 b, f32x4 c)
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
