@@ -99,6 +99,40 @@ constexpr int kDppXor1 = 0xB1;        // quad_perm [1,0,3,2]
 constexpr int kDppXor2 = 0x4E;        // quad_perm [2,3,0,1]
 constexpr int kDppHalfMirror = 0x141; // lane i <-> 7 - i inside each 8-lane half row
 
+// Addresses of the time loops (round 8).  A wave-uniform pointer pinned in an SGPR pair and opaque to the compiler: the 32-bit per-lane byte
+// offset added to it afterwards stays the VGPR offset of `global_load/store v_off, v_data, s[base:base+1] offset:imm`, and the step advances the
+// base on the scalar unit.  Left alone the compiler folds the lane's part into a 64-bit per-lane address ahead of the loop and moves THAT with a
+// v_lshl_add_u64 per access and step.
+// (The pin hides where the pointer came from, so it is typed as global memory by hand: a generic pointer would be accessed with flat_*.)
+#define TFMPC_GLOBAL __attribute__((address_space(1)))
+using gbytes = TFMPC_GLOBAL char *;
+__device__ __forceinline__ gbytes uniform_base(const float *p)
+{
+    gbytes g = (gbytes)p;
+    asm("" : "+s"(g));
+    return g;
+}
+// The lane's offset is pinned where it is used: widened to 64 bits ahead of the loop it would no longer be recognised as the 32-bit VGPR offset.
+// Pinned IN PLACE (the variable itself passes through the empty asm), so that no copy of it is made per use.
+__device__ __forceinline__ unsigned here(unsigned &off)
+{
+    asm volatile("" : "+v"(off));
+    return off;
+}
+template <class V>
+__device__ __forceinline__ V gload(gbytes base, unsigned &off) { return *reinterpret_cast<const TFMPC_GLOBAL V *>(base + here(off)); }
+template <class V>
+__device__ __forceinline__ void gstore(gbytes base, unsigned &off, V v) { *reinterpret_cast<TFMPC_GLOBAL V *>(base + here(off)) = v; }
+// A loop-invariant LDS index pinned in a VGPR: its constant part (beyond the offset field of ds_read2 / ds_write2) is added once, not per step.
+__device__ __forceinline__ int pinned(int v)
+{
+    asm("" : "+v"(v));
+    return v;
+}
+// 16-byte row segments of the chunk epilogue: the LDS rows are 8-byte aligned (kZld even), the destination is whatever the caller's pointer is
+typedef float f32x4_lds __attribute__((ext_vector_type(4), aligned(8)));
+typedef float f32x4_any __attribute__((ext_vector_type(4), aligned(4)));
+
 // EXACT: n == 16 and m == 8 (no guards, vector gain stores).  Otherwise the instance is
 // embedded in the 16 x 8 tile grid: states n..15 and actions m..7 are zero rows/columns of
 // F~ and C~, with a unit diagonal on the padded part of C_uu so the elimination stays regular
@@ -188,11 +222,18 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
         f32x4 Vd = Cd00, vd = vterm;
         float cst = 0.0f;
         int min_pivot_bits = 0x3f800000;     // smallest pivot seen, as float bits (int order == float order for >= 0)
-        for (int idx = lane; idx < kZs; idx += kWave) lds[idx] = 0.0f;   // pad columns stay 0
         constexpr int kZero = kMs + 25 * 8;      // columns 25..31 of the elimination input are never written
+        // ... and are the only part of the slice that is read before it is written: column 25 as the zero operand (t01_src, g1_src below), all of
+        // them by the elimination's lanes 25..31 (whose results nobody reads).  q_x overwrites 28, 29 every step; every step writes the columns
+        // 0..24 of the input and ALL of K~ before it reads them, and the transpose staging likewise.
+        if (lane < kKs - kZero) lds[kZero + lane] = 0.0f;
         constexpr int kQx = kMs + 28 * 8;        // q_x staging in pad columns 28, 29
         const int t01_src = (i == M) ? kQx + 4 * q : kZero;
         const int g1_src = (i == M) ? kKs + (N + M) * 8 + q : kZero + q;
+        // loop-invariant addresses of the step (pinned: see above)
+        const int g0_src = pinned(kKs + i * 8 + q);                  // K[4s+q][i]
+        const int vt_dst = pinned(kZs + 4 * q * kVtLd + i);          // V' transpose staging, element [row 4q][column i]
+        unsigned offK = 8u * lane, offk = 4u * lane;                 // byte offsets of this lane's gains inside a step (EXACT)
         __syncthreads();
 
         // One sweep step.  LAST (a std::bool_constant) marks the step t == 0 of a launch without value outputs, peeled below: nothing reads
@@ -289,7 +330,7 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     const float ax = lds[kMs + i * 8 + 4 * s2 + q];            // Q_xu[i][4s+q] = Q_ux[4s+q][i]
-                    const float g0 = lds[kKs + i * 8 + 4 * s2 + q];            // K[4s+q][i]
+                    const float g0 = lds[g0_src + 4 * s2];                     // K[4s+q][i]
                     const float g1 = lds[g1_src + 4 * s2];                     // K~[4s+q][24] in lanes i == 8
                     T00 = mfma(ax, g0, T00);
                     vacc = mfma(ax, g1, vacc);
@@ -301,9 +342,9 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
                 // Stored element by element as [row 4q+r][column i] (conflict-free: 80 q + i covers the 64 banks once) and read back as ONE
                 // 16-byte row segment [row i][4q .. 4q+3] = V'^T, which lands in a register quad that pairs with T00 for the packed adds.
                 {
-                    float *vt = &lds[kZs];                    // rollout buffer, idle during the sweep
+                    const float *vt = &lds[kZs];              // rollout buffer, idle during the sweep
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) vt[(4 * q + r) * kVtLd + i] = T00[r];
+                    for (int r = 0; r < 4; ++r) lds[vt_dst + r * kVtLd] = T00[r];
                     lds_sync();
                     const f32x4 Tt = *reinterpret_cast<const f32x4 *>(&vt[i * kVtLd + 4 * q]);
 #pragma unroll
@@ -318,8 +359,8 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
                 kv.x = lds[kKs + (2 * jc) * 8 + ka];
                 kv.y = lds[kKs + (2 * jc + 1) * 8 + ka];
                 if (EXACT) {
-                    *reinterpret_cast<float2 *>(&Kg[(size_t)t * (M * N) + 2 * lane]) = kv;
-                    if (lane < M) kg[(size_t)t * M + lane] = lds[kKs + 24 * 8 + lane];
+                    gstore(uniform_base(Kg + (size_t)t * (M * N)), offK, f32x2{kv.x, kv.y});
+                    if (lane < M) gstore(uniform_base(kg + (size_t)t * M), offk, lds[kKs + 24 * 8 + lane]);
                 } else {
                     if (ka < m && 2 * jc < n) Kg[(size_t)t * m * n + ka * n + 2 * jc] = kv.x;
                     if (ka < m && 2 * jc + 1 < n) Kg[(size_t)t * m * n + ka * n + 2 * jc + 1] = kv.y;
@@ -418,10 +459,13 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
             if (EXACT || lane < n) xs[lane] = x;
         }
         // gains of step t for this lane: K[ka][2jc], K[ka][2jc+1], k[ka]
+        // EXACT: one per-lane byte offset each for K and k, fixed for the whole rollout; the (clamped, wave-uniform) step moves an SGPR base
+        unsigned offK = 8u * lane, offk = 4u * ka;
         auto load_gain = [&](int t, float2 &Kv, float &kv) {
             if (EXACT) {
-                Kv = *reinterpret_cast<const float2 *>(&Kg[(size_t)t * (M * N) + 2 * lane]);
-                kv = kg[(size_t)t * M + ka];
+                const f32x2 K2 = gload<f32x2>(uniform_base(Kg + (size_t)t * (M * N)), offK);
+                Kv = float2{K2[0], K2[1]};
+                kv = gload<float>(uniform_base(kg + (size_t)t * M), offk);
             } else {
                 const bool row = ka < m;
                 Kv.x = (row && 2 * jc < n) ? Kg[(size_t)t * m * n + ka * n + 2 * jc] : 0.0f;
@@ -466,51 +510,76 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
             }
         };
 
+        // One rollout step: row tt of the chunk buffer, step t of the horizon, gains from one slot of the ring.
+        auto rollout_step = [&](const int tt, const int t, float2 &KRd, float &kRd, auto REFILL) __attribute__((always_inline)) {
+            float *zt = zs + tt * kZld;
+            const float2 Kc = KRd;
+            const float kc = kRd;
+            // u = K x + k                                              lqr.py:143
+            const float2 xv = *reinterpret_cast<const float2 *>(&zt[2 * jc]);
+            float u = fmaf(Kc.x, xv.x, Kc.y * xv.y);
+            u += dpp<kDppXor1>(u);
+            u += dpp<kDppXor2>(u);
+            u += dpp<kDppHalfMirror>(u);
+            u += kc;
+            // this slot's next step -- UNCONDITIONAL (clamped: the last turns reload the final step): behind a branch the compiler
+            // can no longer count the loads in flight and waits for all of them.  Issued once the slot's gains are consumed, so that it is
+            // refilled IN PLACE (issued ahead of them the new gains need registers of their own and are copied into the slot afterwards).
+            if constexpr (decltype(REFILL)::value) load_gain(t + kRing < T ? t + kRing : T - 1, KRd, kRd);
+            zt[N + ka] = u;                      // all eight lanes of the row hold the same sum
+            lds_sync();
+            // x' = F z + f                                              lqr.py:36-39
+            float xn = f_part;
+            const float2 *zp = reinterpret_cast<const float2 *>(&zt[6 * fc]);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float2 z2 = zp[j];
+                xn = fmaf(Fr[2 * j], z2.x, xn);
+                xn = fmaf(Fr[2 * j + 1], z2.y, xn);
+            }
+            xn += dpp<kDppXor1>(xn);
+            xn += dpp<kDppXor2>(xn);
+            zt[kZld + fi] = xn;                  // likewise: the four lanes of row fi agree
+            lds_sync();
+        };
+
+        // chunk epilogue (EXACT): 16 bytes per lane -- four lanes per state row (64 B), two per action row (32 B); sources fixed per lane
+        const int xrow = lane >> 2, urow = lane >> 1;
+        const float *xsrc = zs + (1 + xrow) * kZld + 4 * (lane & 3);
+        const float *usrc = zs + urow * kZld + N + 4 * (lane & 1);
+        unsigned off16 = 16u * lane;
+
         for (int t0 = 0; t0 < T; t0 += kTC) {
             const int tc = (T - t0 < kTC) ? (T - t0) : kTC;
-            for (int tb = 0; tb < tc; tb += kRing) {
+            int tb = 0;
+            for (; tb + kRing <= tc; tb += kRing) {
 #pragma unroll
-                for (int d = 0; d < kRing; ++d) {
-                    const int tt = tb + d;
-                    if (tt >= tc) break;
-                    const int t = t0 + tt;
-                    float *zt = zs + tt * kZld;
-                    const float2 Kc = KR[d];
-                    const float kc = kR[d];
-                    // this slot's next step -- UNCONDITIONAL (clamped: the last turns reload the final step): behind a branch the compiler
-                    // can no longer count the loads in flight and waits for all of them
-                    load_gain(t + kRing < T ? t + kRing : T - 1, KR[d], kR[d]);
-                    // u = K x + k                                              lqr.py:143
-                    const float2 xv = *reinterpret_cast<const float2 *>(&zt[2 * jc]);
-                    float u = fmaf(Kc.x, xv.x, Kc.y * xv.y);
-                    u += dpp<kDppXor1>(u);
-                    u += dpp<kDppXor2>(u);
-                    u += dpp<kDppHalfMirror>(u);
-                    u += kc;
-                    zt[N + ka] = u;                      // all eight lanes of the row hold the same sum
-                    lds_sync();
-                    // x' = F z + f                                              lqr.py:36-39
-                    float xn = f_part;
-                    const float2 *zp = reinterpret_cast<const float2 *>(&zt[6 * fc]);
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const float2 z2 = zp[j];
-                        xn = fmaf(Fr[2 * j], z2.x, xn);
-                        xn = fmaf(Fr[2 * j + 1], z2.y, xn);
-                    }
-                    xn += dpp<kDppXor1>(xn);
-                    xn += dpp<kDppXor2>(xn);
-                    zt[kZld + fi] = xn;                  // likewise: the four lanes of row fi agree
-                    lds_sync();
-                }
+                for (int d = 0; d < kRing; ++d) rollout_step(tb + d, t0 + tb + d, KR[d], kR[d], std::true_type{});
             }
+            // Fewer than kRing steps are left in the LAST chunk only (every other chunk is whole turns of the ring, so slot d still holds step
+            // tb + d): they take their gains from their slots and refill nothing.  Kept out of the loop above: an exit from the middle of a turn
+            // makes the compiler rotate the ring through copies at the back edge.
+#pragma unroll
+            for (int d = 0; d < kRing - 1; ++d)
+                if (tb + d < tc) rollout_step(tb + d, t0 + tb + d, KR[d], kR[d], std::false_type{});
             // chunk epilogue: stage costs on the matrix cores, bulk coalesced stores
             chunk_costs(tc, cs + t0);
             if (EXACT) {
-                for (int idx = lane; idx < tc * N; idx += kWave)
-                    xs[(size_t)(t0 + 1) * N + idx] = zs[(1 + idx / N) * kZld + (idx & (N - 1))];
-                for (int idx = lane; idx < tc * M; idx += kWave)
-                    us[(size_t)t0 * M + idx] = zs[(idx / M) * kZld + N + (idx & (M - 1))];
+                // rows 1..tc of the buffer are x_{t0+1..t0+tc}, rows 0..tc-1 hold u_{t0..t0+tc-1}: every iteration is one LDS read and one
+                // store at immediate offsets from a fixed source and a chunk-uniform destination, the row guard stores exactly tc rows
+                const gbytes xdst = uniform_base(xs + (size_t)(t0 + 1) * N), udst = uniform_base(us + (size_t)t0 * M);
+#pragma unroll
+                for (int r0 = 0; r0 < kTC; r0 += kWave / 4) {
+                    if (r0 >= tc) break;
+                    if (r0 + xrow < tc)
+                        gstore<f32x4_any>(xdst + r0 * (N * 4), off16, *reinterpret_cast<const f32x4_lds *>(xsrc + r0 * kZld));
+                }
+#pragma unroll
+                for (int r0 = 0; r0 < kTC; r0 += kWave / 2) {
+                    if (r0 >= tc) break;
+                    if (r0 + urow < tc)
+                        gstore<f32x4_any>(udst + r0 * (M * 4), off16, *reinterpret_cast<const f32x4_lds *>(usrc + r0 * kZld));
+                }
             } else {
                 for (int idx = lane; idx < tc * n; idx += kWave)
                     xs[(size_t)(t0 + 1) * n + idx] = zs[(1 + idx / n) * kZld + idx % n];
