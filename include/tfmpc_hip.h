@@ -219,6 +219,33 @@ int tfmpc_tvlqr_solve_f32(int B, int n, int m, int T,
                           float *K, float *k, float *V, float *v, float *cst, int32_t *status,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ----------------------------------------- time-varying LQR, double precision --------
+ * The TV-LQR block above with every value a double: the same problem, operand strides (in elements),
+ * outputs, statuses, error codes and B == 0 no-op; status stays int32.  One wavefront per instance, the three matrix
+ * products of a step on v_mfma_f64_16x16x4_f64, for n <= 32 and m <= 32 (kernel_name_f64: "tv_f64_wave16" for n <= 16
+ * and m <= 16, "tv_f64_wave32" otherwise); beyond: TFMPC_ERR_UNSUPPORTED ("unsupported").  The split backward + forward
+ * calls give the bits of the fused solve.  workspace_bytes_f64 = B T m (n + 1) 8.  There are no f64 gradient calls. */
+size_t tfmpc_tvlqr_workspace_bytes_f64(int B, int n, int m, int T);
+const char *tfmpc_tvlqr_kernel_name_f64(int n, int m, int T);
+int tfmpc_tvlqr_backward_f64(int B, int n, int m, int T,
+                             const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                             const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                             const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                             double *K, double *k, double *V, double *v, double *cst, int32_t *status, void *stream);
+int tfmpc_tvlqr_forward_f64(int B, int n, int m, int T,
+                            const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                            const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                            const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                            const double *K, long strideK, const double *k, long stride_k,
+                            const double *x0, double *states, double *actions, double *costs, void *stream);
+int tfmpc_tvlqr_solve_f64(int B, int n, int m, int T,
+                          const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                          const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                          const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                          const double *x0, double *states, double *actions, double *costs,
+                          double *K, double *k, double *V, double *v, double *cst, int32_t *status,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------ TV-LQR gradients --------
  * Vector-Jacobian product of tfmpc_tvlqr_solve_f32: given the forward's states[B][T+1][n] (states[b][0]
  * is x0) and actions[B][T][m], and upstream gradients g_states[B][T+1][n], g_actions[B][T][m], g_costs[B][T+1] (each

@@ -50,6 +50,12 @@ _SIGNATURES.update({
     "tfmpc_tvlqr_backward_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P]),
     "tfmpc_tvlqr_forward_f32": (_I, _TV_MODEL + [_P, _L, _P, _L, _P, _P, _P, _P, _P]),
     "tfmpc_tvlqr_solve_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    # the double-precision twins: the same argument lists, every float * a double *
+    "tfmpc_tvlqr_workspace_bytes_f64": (_Z, [_I, _I, _I, _I]),
+    "tfmpc_tvlqr_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I]),
+    "tfmpc_tvlqr_backward_f64": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P]),
+    "tfmpc_tvlqr_forward_f64": (_I, _TV_MODEL + [_P, _L, _P, _L, _P, _P, _P, _P, _P]),
+    "tfmpc_tvlqr_solve_f64": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "tfmpc_tvlqr_vjp_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     # states actions, g_states g_actions g_costs, dF df dC dc (+ batch, time strides), dCfin dcfin dx0 (+ batch stride)
     "tfmpc_tvlqr_vjp_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3 + [_P, _P, _Z, _P]),

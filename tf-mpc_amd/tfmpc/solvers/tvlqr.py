@@ -8,6 +8,10 @@ Operand shapes: ``F`` is ``[T, n, d]`` (shared by the batch) or ``[B, T, n, d]``
 (vectors as ``[..., size]`` or columns ``[..., size, 1]``).  A time axis of size 1 is broadcast over the horizon with
 time stride 0 (no copy).  ``C_final`` is ``[n, n]`` or ``[B, n, n]``, ``c_final`` ``[n]`` / ``[n, 1]`` / ``[B, n(, 1)]``.
 ``C_t`` and ``C_final`` must be symmetric (the kernels' precondition; there is no general-C path).
+
+Precision: the default ``dtype=torch.float32`` casts every operand to fp32, float64 inputs included, silently.  Pass
+``dtype=torch.float64`` for the double-precision kernels (``tfmpc_tvlqr_*_f64``, DESIGN.md 3.14, n <= 32 and m <= 32):
+operands, ``x0`` and every output then stay in double.  Gradients are served in fp32 only.
 """
 
 import numpy as np
@@ -19,24 +23,50 @@ from tfmpc.solvers.lqr import LQR, Policy, ValueFn, _as_column, _as_f32
 from tfmpc.utils import trajectory
 
 
+_DTYPES = (torch.float32, torch.float64)
+
+
+def _check_dtype(dtype):
+    if dtype not in _DTYPES:
+        raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype!r}")
+    return dtype
+
+
+def _as_dtype(a, device, dtype):
+    """``lqr._as_f32`` for either precision: a detached copy on ``device`` in ``dtype``."""
+    if dtype == torch.float32:
+        return _as_f32(a, device)
+    if isinstance(a, torch.Tensor):
+        return a.detach().to(device=device, dtype=dtype)
+    return torch.as_tensor(np.asarray(a, dtype=np.float64), device=device)
+
+
 def _is_symmetric(t):
     if t.numel() == 0:
         return True
-    return bool((t - t.transpose(-1, -2)).abs().amax() <= 1e-6 * t.abs().amax())
+    tol = 1e-12 if t.dtype == torch.float64 else 1e-6
+    return bool((t - t.transpose(-1, -2)).abs().amax() <= tol * t.abs().amax())
 
 
 class TimeVaryingLQR:
 
-    def __init__(self, F, f, C, c, C_final=None, c_final=None, device=None, symmetric=None):
+    def __init__(self, F, f, C, c, C_final=None, c_final=None, device=None, symmetric=None, dtype=torch.float32):
         """``symmetric``: ``None`` checks ``C`` (and ``C_final``) once on the device; ``True`` states it and skips the
-        check (no synchronisation); ``False`` raises -- only symmetric costs are served."""
+        check (no synchronisation); ``False`` raises -- only symmetric costs are served.
+
+        ``dtype``: ``torch.float32`` (default) stores fp32 copies of the operands -- float64 inputs are cast down
+        silently, as they always were -- and runs the fp32 kernels.  ``torch.float64`` keeps operands, ``x0`` and every
+        output in double and runs ``tfmpc_tvlqr_*_f64``; the symmetry check then uses 1e-12 relative in place of 1e-6,
+        and an operand or ``x0`` that requires grad is refused (gradients: ``dtype=torch.float32``)."""
+        self.dtype = _check_dtype(dtype)
+        self._sfx = "f64" if dtype == torch.float64 else "f32"
         self.device = torch.device(device) if device is not None else _hip.default_device()
         # The caller's TENSOR operands, where the differentiable path starts (numpy operands cannot require grad: None).
         # A reference, not a copy -- but it keeps them alive as long as the solver, e.g. an fp64 / CPU original of a
         # large per-instance model next to its fp32 device copy; drop the solver (or the originals) to free them.
         self._sources = tuple(a if isinstance(a, torch.Tensor) else None for a in (F, f, C, c, C_final, c_final))
         self.last_grad_status = None
-        F, f, C, c = (_as_f32(a, self.device) for a in (F, f, C, c))
+        F, f, C, c = (self._cast(a) for a in (F, f, C, c))
         if F.dim() not in (3, 4):
             raise ValueError(f"F must be [T, n, d] or [B, T, n, d], got {tuple(F.shape)}")
         n, d = F.shape[-2], F.shape[-1]
@@ -56,7 +86,7 @@ class TimeVaryingLQR:
         if (C_final is None) != (c_final is None):
             raise ValueError("give both C_final and c_final, or neither")
         if C_final is not None:
-            C_final, c_final = _as_f32(C_final, self.device), _as_f32(c_final, self.device)
+            C_final, c_final = self._cast(C_final), self._cast(c_final)
             if C_final.dim() not in (2, 3) or tuple(C_final.shape[-2:]) != (n, n):
                 raise ValueError(f"C_final must be [n, n] or [B, n, n] with n={n}, got {tuple(C_final.shape)}")
             if c_final.dim() == 1 or (c_final.dim() == 2 and c_final.shape != (n, 1)):
@@ -75,6 +105,15 @@ class TimeVaryingLQR:
             symmetric = _is_symmetric(self.C) and (C_final is None or _is_symmetric(C_final))
         if not symmetric:
             raise ValueError("C (and C_final) must be symmetric: the time-varying kernels serve symmetric costs only")
+
+    def _cast(self, a):
+        return _as_dtype(a, self.device, self.dtype)
+
+    def _refuse_grad(self, *more):
+        """The double-precision path has no gradient kernels: say so before any launch, never downcast."""
+        if self.dtype == torch.float64 and tvlqr_grad.wants_grad(*self._sources, *more):
+            raise NotImplementedError("gradients of the time-varying LQR are served in fp32 only: build the problem with "
+                                      "dtype=torch.float32, or detach the operands and x0 for a dtype=torch.float64 solve")
 
     @staticmethod
     def _vector(t, size, name):
@@ -96,21 +135,50 @@ class TimeVaryingLQR:
         return t.contiguous()
 
     @classmethod
-    def from_lqr(cls, lqr, T, C_final=None, c_final=None):
+    def time_invariant(cls, F, f, C, c, T, C_final=None, c_final=None, device=None, symmetric=None, dtype=torch.float32):
+        """The time-invariant problem ``F, f, C, c`` over ``T`` steps, from :class:`~tfmpc.solvers.lqr.LQR`'s operand
+        shapes (``[n, d]`` or ``[B, n, d]``; vectors ``[size]``, ``[size, 1]`` or with a leading batch axis): each operand
+        is converted once and expanded along a time axis of stride 0, no copy per step.  With ``dtype=torch.float64`` this
+        is the double-precision solve of an ``LQR`` problem; ``LQR`` itself stores fp32 copies."""
+        T = int(T)
+        if T < 1:
+            raise ValueError("the horizon must be at least 1 step")
+        dtype = _check_dtype(dtype)
+        dev = torch.device(device) if device is not None else _hip.default_device()
+
+        def convert(a):             # tensors stay in the caller's autograd graph (the fp32 gradients start there)
+            if isinstance(a, torch.Tensor):
+                return a.to(device=dev, dtype=dtype)
+            return _as_dtype(a, dev, dtype)
+        F, f, C, c = (convert(a) for a in (F, f, C, c))
+        if F.dim() not in (2, 3):
+            raise ValueError(f"F must be [n, d] or [B, n, d], got {tuple(F.shape)}")
+        n, d = F.shape[-2], F.shape[-1]
+        f, c = _as_column(f, n), _as_column(c, d)
+        views = [t.unsqueeze(-3).expand(*t.shape[:-2], T, *t.shape[-2:]) for t in (F, f, C, c)]
+        return cls(*views, C_final, c_final, device=dev, symmetric=symmetric, dtype=dtype)
+
+    @classmethod
+    def from_lqr(cls, lqr, T, C_final=None, c_final=None, dtype=None):
         """The time-invariant problem of ``lqr`` over ``T`` steps as a TV problem: views with time stride 0.  ``C_final``,
         ``c_final`` replace the default final cost, e.g. ``from_lqr(lqr, T, ss.P, ss.p)`` with ``ss = lqr.steady_state()``:
-        the stationary value function as terminal cost of a short horizon.  ``C_final`` must be symmetric."""
+        the stationary value function as terminal cost of a short horizon.  ``C_final`` must be symmetric.
+
+        ``dtype=None`` is the ``lqr``'s own fp32.  ``torch.float64`` upcasts the operands ``lqr`` STORES, which are fp32:
+        their rounding to fp32 has already happened (for a problem posed in double, use :meth:`time_invariant`)."""
         T = int(T)
-        views = [t.unsqueeze(-3).expand(*t.shape[:-2], T, *t.shape[-2:]) for t in (lqr.F, lqr.f, lqr.C, lqr.c)]
+        dtype = torch.float32 if dtype is None else _check_dtype(dtype)
+        views = [t.unsqueeze(-3).expand(*t.shape[:-2], T, *t.shape[-2:])
+                 for t in (op.to(dtype) for op in (lqr.F, lqr.f, lqr.C, lqr.c))]
         if not lqr.symmetric_cost:
             raise ValueError("only a symmetric C has a time-varying counterpart")
         if C_final is None and c_final is None:
-            return cls(*views, device=lqr.device, symmetric=True)
+            return cls(*views, device=lqr.device, symmetric=True, dtype=dtype)
         if C_final is None or c_final is None:
             raise ValueError("give both C_final and c_final, or neither")
         # C is known symmetric; C_final is checked here, NaN entries (a flagged steady-state instance) left out of the test
-        symmetric = _is_symmetric(torch.nan_to_num(_as_f32(C_final, lqr.device), nan=0.0))
-        return cls(*views, C_final, c_final, device=lqr.device, symmetric=symmetric)
+        symmetric = _is_symmetric(torch.nan_to_num(_as_dtype(C_final, lqr.device, dtype), nan=0.0))
+        return cls(*views, C_final, c_final, device=lqr.device, symmetric=symmetric, dtype=dtype)
 
     # -- properties ----------------------------------------------------------------
     @property
@@ -130,16 +198,16 @@ class TimeVaryingLQR:
         return t_op.select(-3, t if t_op.shape[-3] > 1 else 0)
 
     def transition(self, x, u, t):
-        z = torch.cat([_as_f32(x, self.device), _as_f32(u, self.device)], dim=-2)
+        z = torch.cat([self._cast(x), self._cast(u)], dim=-2)
         return self._step(self.F, t) @ z + self._step(self.f, t)
 
     def cost(self, x, u, t):
-        z = torch.cat([_as_f32(x, self.device), _as_f32(u, self.device)], dim=-2)
+        z = torch.cat([self._cast(x), self._cast(u)], dim=-2)
         zt = z.transpose(-1, -2)
         return 0.5 * (zt @ self._step(self.C, t)) @ z + zt @ self._step(self.c, t)
 
     def final_cost(self, x):
-        x = _as_f32(x, self.device)
+        x = self._cast(x)
         n = self.state_size
         if self.C_final is not None:
             Cf, cf = self.C_final, self.c_final
@@ -164,7 +232,18 @@ class TimeVaryingLQR:
         return args
 
     def _prep_x0(self, x0):
-        return LQR._prep_x0(self, x0)
+        if self.dtype == torch.float32:
+            return LQR._prep_x0(self, x0)
+        n = self.state_size
+        x0 = _as_column(self._cast(x0), n)
+        if tuple(x0.shape[-2:]) != (n, 1) or x0.dim() not in (2, 3):
+            raise ValueError(f"x0 must be [n,1] or [B,n,1] with n={n}, got {tuple(x0.shape)}")
+        return x0.contiguous()
+
+    def _entry(self, lib, name):
+        """``tfmpc_tvlqr_<name>_f32`` or its ``_f64`` twin, and the name for error messages."""
+        full = f"tfmpc_tvlqr_{name}_{self._sfx}"
+        return getattr(lib, full), full
 
     def _resolve_batch(self, x0=None):
         return LQR._resolve_batch(self, x0)
@@ -174,7 +253,10 @@ class TimeVaryingLQR:
         """The Riccati recursion: ``(Policy, ValueFn)``.  ``differentiable=True``: when autograd is recording and a tensor
         operand requires grad, their tensors are in the autograd graph, with gradients from
         ``tfmpc_tvlqr_backward_vjp_f32`` (tfmpc/solvers/tvlqr_backward_grad.py); the backward pass's
-        per-instance status goes to ``last_grad_status``.  The outputs are the same bits as without grad."""
+        per-instance status goes to ``last_grad_status``.  The outputs are the same bits as without grad.
+        With ``dtype=torch.float64`` that request raises ``NotImplementedError`` (gradients are fp32 only)."""
+        if differentiable:
+            self._refuse_grad()
         if differentiable and tvlqr_grad.wants_grad(*self._sources):
             from tfmpc.solvers import tvlqr_backward_grad as bgrad
             problem = tvlqr_grad.Problem(self._backward_launch, lambda: self, True, self)
@@ -186,21 +268,22 @@ class TimeVaryingLQR:
         return Policy(K, k), ValueFn(V, v, const)
 
     def _backward_launch(self):
-        """One tfmpc_tvlqr_backward_f32 launch: batched ``K, k, V, v, const, status``; sets ``last_status``."""
+        """One tfmpc_tvlqr_backward_f32 / _f64 launch: batched ``K, k, V, v, const, status``; sets ``last_status``."""
         lib = _hip.require_gpu()
         n, m, T = self.state_size, self.action_size, self.horizon
         B = self.batch_size
         Bk = B if B is not None else 1
-        dev = self.device
-        K = torch.empty((Bk, T, m, n), device=dev)
-        k = torch.empty((Bk, T, m, 1), device=dev)
-        V = torch.empty((Bk, T, n, n), device=dev)
-        v = torch.empty((Bk, T, n, 1), device=dev)
-        const = torch.empty((Bk, T, 1, 1), device=dev)
+        dev, dt = self.device, self.dtype
+        K = torch.empty((Bk, T, m, n), device=dev, dtype=dt)
+        k = torch.empty((Bk, T, m, 1), device=dev, dtype=dt)
+        V = torch.empty((Bk, T, n, n), device=dev, dtype=dt)
+        v = torch.empty((Bk, T, n, 1), device=dev, dtype=dt)
+        const = torch.empty((Bk, T, 1, 1), device=dev, dtype=dt)
         status = torch.zeros((Bk,), dtype=torch.int32, device=dev)
-        rc = lib.tfmpc_tvlqr_backward_f32(Bk, n, m, T, *self._model_args(), _hip.ptr(K), _hip.ptr(k), _hip.ptr(V),
-                                          _hip.ptr(v), _hip.ptr(const), _hip.ptr(status), _hip.stream())
-        _hip.check(rc, "tfmpc_tvlqr_backward_f32")
+        fn, name = self._entry(lib, "backward")
+        rc = fn(Bk, n, m, T, *self._model_args(), _hip.ptr(K), _hip.ptr(k), _hip.ptr(V),
+                _hip.ptr(v), _hip.ptr(const), _hip.ptr(status), _hip.stream())
+        _hip.check(rc, name)
         self.last_status = status
         return K, k, V, v, const, status
 
@@ -211,9 +294,11 @@ class TimeVaryingLQR:
         if isinstance(policy, Policy):
             K, k = policy.K, policy.k
         else:
-            tdim = _as_f32(policy[0][0], self.device).dim() - 2
-            K = torch.stack([_as_f32(p[0], self.device) for p in policy], dim=tdim)
-            k = torch.stack([_as_f32(p[1], self.device) for p in policy], dim=tdim)
+            tdim = self._cast(policy[0][0]).dim() - 2
+            K = torch.stack([self._cast(p[0]) for p in policy], dim=tdim)
+            k = torch.stack([self._cast(p[1]) for p in policy], dim=tdim)
+        if self.dtype == torch.float64:      # (a policy computed elsewhere, e.g. in fp32, is taken in double)
+            K, k = self._cast(K), self._cast(k)
         K, k = K.contiguous(), k.contiguous()
         if K.shape[-3] < T:
             raise ValueError(f"policy has {K.shape[-3]} steps, horizon is {T}")
@@ -228,15 +313,16 @@ class TimeVaryingLQR:
         Bk = B if B is not None else 1
         if x0.dim() == 2:
             x0 = x0.unsqueeze(0).expand(Bk, n, 1).contiguous()
-        dev = self.device
-        states = torch.empty((Bk, T + 1, n, 1), device=dev)
-        actions = torch.empty((Bk, T, m, 1), device=dev)
-        costs = torch.empty((Bk, T + 1, 1, 1), device=dev)
+        dev, dt = self.device, self.dtype
+        states = torch.empty((Bk, T + 1, n, 1), device=dev, dtype=dt)
+        actions = torch.empty((Bk, T, m, 1), device=dev, dtype=dt)
+        costs = torch.empty((Bk, T + 1, 1, 1), device=dev, dtype=dt)
         sK = K[0].numel() if pol_batched else 0
         sk = k[0].numel() if pol_batched else 0
-        rc = lib.tfmpc_tvlqr_forward_f32(Bk, n, m, T, *self._model_args(), _hip.ptr(K), sK, _hip.ptr(k), sk,
-                                         _hip.ptr(x0), _hip.ptr(states), _hip.ptr(actions), _hip.ptr(costs), _hip.stream())
-        _hip.check(rc, "tfmpc_tvlqr_forward_f32")
+        fn, name = self._entry(lib, "forward")
+        rc = fn(Bk, n, m, T, *self._model_args(), _hip.ptr(K), sK, _hip.ptr(k), sk,
+                _hip.ptr(x0), _hip.ptr(states), _hip.ptr(actions), _hip.ptr(costs), _hip.stream())
+        _hip.check(rc, name)
         if B is None:
             states, actions, costs = states[0], actions[0], costs[0]
         return states, actions, costs
@@ -252,28 +338,31 @@ class TimeVaryingLQR:
         Bk = B if B is not None else 1
         if x0.dim() == 2:
             x0 = x0.unsqueeze(0).expand(Bk, n, 1).contiguous()
-        dev = self.device
-        out = dict(states=torch.empty((Bk, T + 1, n, 1), device=dev),
-                   actions=torch.empty((Bk, T, m, 1), device=dev),
-                   costs=torch.empty((Bk, T + 1, 1, 1), device=dev),
+        dev, dt = self.device, self.dtype
+        out = dict(states=torch.empty((Bk, T + 1, n, 1), device=dev, dtype=dt),
+                   actions=torch.empty((Bk, T, m, 1), device=dev, dtype=dt),
+                   costs=torch.empty((Bk, T + 1, 1, 1), device=dev, dtype=dt),
                    status=(torch.zeros if Bk == 0 else torch.empty)((Bk,), dtype=torch.int32, device=dev))
         if want_policy:
-            out.update(K=torch.empty((Bk, T, m, n), device=dev), k=torch.empty((Bk, T, m, 1), device=dev))
+            out.update(K=torch.empty((Bk, T, m, n), device=dev, dtype=dt), k=torch.empty((Bk, T, m, 1), device=dev, dtype=dt))
         if want_value:
-            out.update(V=torch.empty((Bk, T, n, n), device=dev), v=torch.empty((Bk, T, n, 1), device=dev),
-                       const=torch.empty((Bk, T, 1, 1), device=dev))
+            out.update(V=torch.empty((Bk, T, n, n), device=dev, dtype=dt), v=torch.empty((Bk, T, n, 1), device=dev, dtype=dt),
+                       const=torch.empty((Bk, T, 1, 1), device=dev, dtype=dt))
         ws_bytes = 0
         if not want_policy:
-            ws_bytes = int(lib.tfmpc_tvlqr_workspace_bytes(Bk, n, m, T))
-            if workspace is None or workspace.numel() * workspace.element_size() < ws_bytes:
-                workspace = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
+            size = dt.itemsize
+            query = lib.tfmpc_tvlqr_workspace_bytes_f64 if dt == torch.float64 else lib.tfmpc_tvlqr_workspace_bytes
+            ws_bytes = int(query(Bk, n, m, T))
+            if workspace is None or workspace.numel() * workspace.element_size() < ws_bytes or workspace.data_ptr() % size:
+                workspace = torch.empty((max(ws_bytes, size) + size - 1) // size, dtype=dt, device=dev)
             ws_bytes = workspace.numel() * workspace.element_size()
-        rc = lib.tfmpc_tvlqr_solve_f32(Bk, n, m, T, *self._model_args(), _hip.ptr(x0),
-                                       _hip.ptr(out["states"]), _hip.ptr(out["actions"]), _hip.ptr(out["costs"]),
-                                       _hip.ptr(out.get("K")), _hip.ptr(out.get("k")), _hip.ptr(out.get("V")),
-                                       _hip.ptr(out.get("v")), _hip.ptr(out.get("const")), _hip.ptr(out["status"]),
-                                       _hip.ptr(workspace), ws_bytes, _hip.stream())
-        _hip.check(rc, "tfmpc_tvlqr_solve_f32")
+        fn, name = self._entry(lib, "solve")
+        rc = fn(Bk, n, m, T, *self._model_args(), _hip.ptr(x0),
+                _hip.ptr(out["states"]), _hip.ptr(out["actions"]), _hip.ptr(out["costs"]),
+                _hip.ptr(out.get("K")), _hip.ptr(out.get("k")), _hip.ptr(out.get("V")),
+                _hip.ptr(out.get("v")), _hip.ptr(out.get("const")), _hip.ptr(out["status"]),
+                _hip.ptr(workspace), ws_bytes, _hip.stream())
+        _hip.check(rc, name)
         self.last_status = out["status"]
         out["batched"] = B is not None
         out["workspace"] = workspace
@@ -281,7 +370,9 @@ class TimeVaryingLQR:
 
     def solve(self, x0):
         """A :class:`Trajectory`; with autograd recording and an operand or ``x0`` requiring grad, a
-        :class:`~tfmpc.solvers.tvlqr_grad.TensorTrajectory` differentiable through ``tfmpc_tvlqr_vjp_f32``."""
+        :class:`~tfmpc.solvers.tvlqr_grad.TensorTrajectory` differentiable through ``tfmpc_tvlqr_vjp_f32``
+        (``dtype=torch.float64``: ``NotImplementedError`` instead; gradients are fp32 only)."""
+        self._refuse_grad(x0)
         if tvlqr_grad.wants_grad(*self._sources, x0):
             states, actions, costs = self.solve_tensors(x0)
             return tvlqr_grad.TensorTrajectory(states, actions, costs)
@@ -293,7 +384,9 @@ class TimeVaryingLQR:
 
     def solve_tensors(self, x0):
         """``(states[(B,)T+1,n,1], actions[(B,)T,m,1], costs[(B,)T+1,1,1])`` as tensors; in the autograd graph of the
-        caller's operands and ``x0`` when autograd is recording (gradients: tfmpc/solvers/tvlqr_grad.py)."""
+        caller's operands and ``x0`` when autograd is recording (gradients: tfmpc/solvers/tvlqr_grad.py; fp32 only,
+        ``dtype=torch.float64`` raises ``NotImplementedError`` there)."""
+        self._refuse_grad(x0)
         if not tvlqr_grad.wants_grad(*self._sources, x0):
             out = self.solve_device(x0)
             states, actions, costs = out["states"], out["actions"], out["costs"]

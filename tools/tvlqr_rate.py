@@ -6,9 +6,12 @@
   (ilqr_bw) what a user could run before: tfmpc_ilqr_backward_f32 (mu = 0, unbounded) on the same per-step models
         materialised as l_xx / l_uu / l_xu / l_x / l_u / f_x / f_u -- a backward pass only.
 
+--dtype float64 times (a) and (b) on the double-precision path (tfmpc_tvlqr_solve_f64, DESIGN.md 3.14: 8 000 B per step),
+keeps (lqr) and (ilqr_bw) -- fp32 only -- for scale, and adds the same run's fp32 (a) as a_per_instance_f32.
+
 Prints one JSON object (median / min of --reps timed launches after --warmup) with the roofline fraction of (a) on
 algorithmic bytes (the model read once per pass, two passes, plus trajectory and final cost).
-Usage: python tools/tvlqr_rate.py [--reps 20] [--warmup 3] [--out file.json]"""
+Usage: python tools/tvlqr_rate.py [--dtype float32|float64] [--reps 20] [--warmup 3] [--out file.json]"""
 import argparse
 import json
 import os
@@ -52,7 +55,10 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dtype", choices=("float32", "float64"), default="float32")
     args = ap.parse_args()
+    f64 = args.dtype == "float64"
+    dt, size = (torch.float64, 8) if f64 else (torch.float32, 4)
     _hip.require_gpu()
     lib = _hip.load()
     d = N + M
@@ -60,18 +66,25 @@ def main():
     x0 = tvlqr_ref.make_x0(N, POOL)
     rep = lambda a: torch.as_tensor(a, device="cuda").repeat(B // POOL, *([1] * (a.ndim - 1)))   # noqa: E731
     Fd, fd, Cd, cd, x0d = rep(F), rep(f), rep(C), rep(c), rep(x0)[..., None]
-    res = dict(B=B, n=N, m=M, T=T, kernel=lib.tfmpc_tvlqr_kernel_name(N, M, T).decode())
+    name = lib.tfmpc_tvlqr_kernel_name_f64 if f64 else lib.tfmpc_tvlqr_kernel_name
+    res = dict(B=B, n=N, m=M, T=T, dtype=args.dtype, kernel=name(N, M, T).decode())
 
-    tv = TimeVaryingLQR(Fd, fd, Cd, cd, device="cuda", symmetric=True)
-    ws = torch.empty(int(lib.tfmpc_tvlqr_workspace_bytes(B, N, M, T)) // 4, device="cuda")
-    out = tv.solve_device(x0d, workspace=ws)
-    torch.cuda.synchronize()
-    assert int(out["status"].abs().sum()) == 0
-    res["a_per_instance"] = timed(lambda: tv.solve_device(x0d, workspace=ws), args.reps, args.warmup)
+    def per_instance(dtype):
+        tv = TimeVaryingLQR(Fd.to(dtype), fd.to(dtype), Cd.to(dtype), cd.to(dtype), device="cuda", symmetric=True, dtype=dtype)
+        x0 = x0d.to(dtype)
+        ws = tv.solve_device(x0)["workspace"]
+        out = tv.solve_device(x0, workspace=ws)
+        torch.cuda.synchronize()
+        assert int(out["status"].abs().sum()) == 0
+        return timed(lambda: tv.solve_device(x0, workspace=ws), args.reps, args.warmup), ws
 
-    shared = TimeVaryingLQR(torch.as_tensor(F[0], device="cuda"), torch.as_tensor(f[0], device="cuda"),
-                            torch.as_tensor(C[0], device="cuda"), torch.as_tensor(c[0], device="cuda"), device="cuda", symmetric=True)
-    res["b_shared"] = timed(lambda: shared.solve_device(x0d, workspace=ws), args.reps, args.warmup)
+    res["a_per_instance"], ws = per_instance(dt)
+    shared = TimeVaryingLQR(*(torch.as_tensor(a[0], device="cuda") for a in (F, f, C, c)), device="cuda", symmetric=True, dtype=dt)
+    x0t = x0d.to(dt)
+    res["b_shared"] = timed(lambda: shared.solve_device(x0t, workspace=ws), args.reps, args.warmup)
+    del ws
+    if f64:
+        res["a_per_instance_f32"] = per_instance(torch.float32)[0]
 
     lqr = LQR(Fd[:, 0].contiguous(), fd[:, 0, :, None].contiguous(), Cd[:, 0].contiguous(), cd[:, 0, :, None].contiguous(),
               device="cuda", symmetric=True)
@@ -99,13 +112,12 @@ def main():
         _hip.check(rc, "tfmpc_ilqr_backward_f32")
     res["ilqr_backward_baseline"] = timed(ilqr_bw, args.reps, args.warmup)
 
-    model_bytes = T * 4 * (N * d + N + d * d + d)                       # 4 000 B per step
-    per_instance = 2 * model_bytes + 4 * ((T + 1) * N + T * M + (T + 1) + N * N + N)
-    total = B * per_instance
+    model_bytes = T * size * (N * d + N + d * d + d)                    # 4 000 B per step in fp32, 8 000 B in double
+    total = B * (2 * model_bytes + size * ((T + 1) * N + T * M + (T + 1) + N * N + N))
     ta = res["a_per_instance"]["median_ms"] * 1e-3
     res["roofline_a"] = dict(algorithmic_bytes=total, spec_ms=total / SPEC_BW * 1e3, achievable_ms=total / MEASURED_BW * 1e3,
                              fraction_of_spec=total / ta / SPEC_BW, achieved_TBps=total / ta / 1e12,
-                             workspace_roundtrip_bytes_per_instance=2 * T * M * (N + 1) * 4)
+                             workspace_roundtrip_bytes_per_instance=2 * T * M * (N + 1) * size)
     res["b_over_lqr"] = res["b_shared"]["median_ms"] / res["lqr_headline"]["median_ms"]
     res["ilqr_over_a"] = res["ilqr_backward_baseline"]["median_ms"] / res["a_per_instance"]["median_ms"]
     line = json.dumps(res)
