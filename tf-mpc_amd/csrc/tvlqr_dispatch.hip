@@ -1,5 +1,6 @@
-// tvlqr_dispatch.hip -- extern "C" entry points of the time-varying LQR (include/tfmpc_hip.h, TV-LQR block):
-// argument checks, kernel-variant choice, launch.  No allocation, no sync.
+// tvlqr_dispatch.hip -- extern "C" entry points of the time-varying LQR (include/tfmpc_hip.h, TV-LQR block), fp32 and
+// double: argument checks, kernel-variant choice, launch.  No allocation, no sync.  Both precisions run the same
+// checks in the same order; only the support test and the launcher differ.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -11,19 +12,30 @@ using namespace tfmpc;
 
 namespace {
 
+template <class S>
 struct Model {
-    const float *F; long sF_b, sF_t;
-    const float *f; long sf_b, sf_t;
-    const float *C; long sC_b, sC_t;
-    const float *c; long sc_b, sc_t;
-    const float *Cfin; long sCfin_b;
-    const float *cfin; long scfin_b;
+    const S *F; long sF_b, sF_t;
+    const S *f; long sf_b, sf_t;
+    const S *C; long sC_b, sC_t;
+    const S *c; long sc_b, sc_t;
+    const S *Cfin; long sCfin_b;
+    const S *cfin; long scfin_b;
 };
 
-int check_model(int B, int n, int m, int T, const Model &md)
+bool supported(float, int n, int m) { return tvlqr_mfma_supported(n, m) || tvlqr_generic_smem_bytes(n, m) <= kMaxLdsBytes; }
+bool supported(double, int n, int m) { return tvlqr_f64_supported(n, m); }
+
+int launch(const TvLqrArgsT<float> &a, bool bw, bool fw, hipStream_t s)
+{
+    return tvlqr_mfma_supported(a.n, a.m) ? tvlqr_mfma_launch(a, bw, fw, s) : tvlqr_generic_launch(a, bw, fw, s);
+}
+int launch(const TvLqrArgsT<double> &a, bool bw, bool fw, hipStream_t s) { return tvlqr_f64_launch(a, bw, fw, s); }
+
+template <class S>
+int check_model(int B, int n, int m, int T, const Model<S> &md)
 {
     if (B < 0 || n <= 0 || m <= 0 || T <= 0) return TFMPC_ERR_ARG;
-    if (!tvlqr_mfma_supported(n, m) && tvlqr_generic_smem_bytes(n, m) > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
+    if (!supported(S(), n, m)) return TFMPC_ERR_UNSUPPORTED;
     if (B == 0) return TFMPC_OK;                                    // no-op: nothing is read (empty tensors may be NULL)
     if (!md.F || !md.f || !md.C || !md.c) return TFMPC_ERR_ARG;
     if (!md.Cfin != !md.cfin) return TFMPC_ERR_ARG;                 // both or neither
@@ -32,9 +44,10 @@ int check_model(int B, int n, int m, int T, const Model &md)
     return TFMPC_OK;
 }
 
-TvLqrArgs make_args(int B, int n, int m, int T, const Model &md)
+template <class S>
+TvLqrArgsT<S> make_args(int B, int n, int m, int T, const Model<S> &md)
 {
-    TvLqrArgs a{};
+    TvLqrArgsT<S> a{};
     a.B = B; a.n = n; a.m = m; a.T = T;
     a.F = md.F; a.sF_b = md.sF_b; a.sF_t = md.sF_t;
     a.f = md.f; a.sf_b = md.sf_b; a.sf_t = md.sf_t;
@@ -45,110 +58,145 @@ TvLqrArgs make_args(int B, int n, int m, int T, const Model &md)
     return a;
 }
 
-int run(const TvLqrArgs &a, bool bw, bool fw, void *stream)
+template <class S>
+size_t workspace_bytes(int B, int n, int m, int T)
 {
-    if (a.B == 0) return TFMPC_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (tvlqr_mfma_supported(a.n, a.m)) return tvlqr_mfma_launch(a, bw, fw, s);
-    return tvlqr_generic_launch(a, bw, fw, s);
+    if (B <= 0 || n <= 0 || m <= 0 || T <= 0) return 0;
+    return (size_t)B * T * m * (n + 1) * sizeof(S);
 }
 
-}  // namespace
-
-#define TFMPC_TVLQR_MODEL_PARAMS                                                                                    \
-    int B, int n, int m, int T, const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,         \
-        const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t, const float *Cfin, long sCfin_b, \
-        const float *cfin, long scfin_b
-#define TFMPC_TVLQR_MODEL Model{F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b}
-
-namespace tfmpc {
-
-int tvlqr_solve_masked_f32(TFMPC_TVLQR_MODEL_PARAMS, const float *x0, float *states, float *actions, float *costs,
-                           int32_t *status, const uint32_t *mask, void *workspace, size_t workspace_bytes, void *stream)
+template <class S>
+int backward(int B, int n, int m, int T, const Model<S> &md, S *K, S *k, S *V, S *v, S *cst, int32_t *status, void *stream)
 {
-    const Model md = TFMPC_TVLQR_MODEL;
+    int rc = check_model(B, n, m, T, md);
+    if (rc != TFMPC_OK || B == 0) return rc;
+    if (!K || !k) return TFMPC_ERR_ARG;
+    TvLqrArgsT<S> a = make_args(B, n, m, T, md);
+    a.K = K; a.k = k; a.sK = (long)T * m * n; a.sk = (long)T * m;
+    a.V = V; a.v = v; a.cst = cst; a.status = status;
+    return launch(a, true, false, static_cast<hipStream_t>(stream));
+}
+
+template <class S>
+int forward(int B, int n, int m, int T, const Model<S> &md, const S *K, long strideK, const S *k, long stride_k,
+            const S *x0, S *states, S *actions, S *costs, void *stream)
+{
+    int rc = check_model(B, n, m, T, md);
+    if (rc != TFMPC_OK || B == 0) return rc;
+    if (strideK < 0 || stride_k < 0) return TFMPC_ERR_ARG;
+    if (!x0 || !states || !costs || !K || !k || !actions) return TFMPC_ERR_ARG;
+    TvLqrArgsT<S> a = make_args(B, n, m, T, md);
+    a.x0 = x0;
+    a.K = const_cast<S *>(K); a.k = const_cast<S *>(k); a.sK = strideK; a.sk = stride_k;
+    a.states = states; a.actions = actions; a.costs = costs;
+    return launch(a, false, true, static_cast<hipStream_t>(stream));
+}
+
+// mask != NULL: the masked sweep (fp32 only, tvlqr_solve_masked_f32)
+template <class S>
+int solve(int B, int n, int m, int T, const Model<S> &md, const S *x0, S *states, S *actions, S *costs, S *K, S *k,
+          S *V, S *v, S *cst, int32_t *status, const uint32_t *mask, void *workspace, size_t workspace_bytes_given,
+          void *stream)
+{
     int rc = check_model(B, n, m, T, md);
     if (rc != TFMPC_OK || B == 0) return rc;
     if (!x0 || !states || !costs || !actions) return TFMPC_ERR_ARG;
     if (mask && m > 32) return TFMPC_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < tfmpc_tvlqr_workspace_bytes(B, n, m, T)) return TFMPC_ERR_WORKSPACE;
-    float *w = static_cast<float *>(workspace);
-    TvLqrArgs a = make_args(B, n, m, T, md);
+    if (!K || !k) {
+        // gains are not a requested output: keep them in caller-provided scratch
+        if (!workspace || workspace_bytes_given < workspace_bytes<S>(B, n, m, T)) return TFMPC_ERR_WORKSPACE;
+        S *w = static_cast<S *>(workspace);
+        if (!K) K = w;
+        if (!k) k = w + (size_t)B * T * m * n;
+    }
+    TvLqrArgsT<S> a = make_args(B, n, m, T, md);
     a.x0 = x0;
-    a.K = w; a.k = w + (size_t)B * T * m * n; a.sK = (long)T * m * n; a.sk = (long)T * m;
+    a.K = K; a.k = k; a.sK = (long)T * m * n; a.sk = (long)T * m;
+    a.V = V; a.v = v; a.cst = cst;
     a.states = states; a.actions = actions; a.costs = costs; a.status = status;
     a.mask = mask;
-    return run(a, true, true, stream);
+    return launch(a, true, true, static_cast<hipStream_t>(stream));
+}
+
+}  // namespace
+
+#define TFMPC_TVLQR_MODEL_PARAMS(S)                                                                                     \
+    int B, int n, int m, int T, const S *F, long sF_b, long sF_t, const S *f, long sf_b, long sf_t, const S *C, long sC_b, \
+        long sC_t, const S *c, long sc_b, long sc_t, const S *Cfin, long sCfin_b, const S *cfin, long scfin_b
+#define TFMPC_TVLQR_MODEL(S) \
+    B, n, m, T, Model<S>{F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b}
+
+namespace tfmpc {
+
+int tvlqr_solve_masked_f32(TFMPC_TVLQR_MODEL_PARAMS(float), const float *x0, float *states, float *actions, float *costs,
+                           int32_t *status, const uint32_t *mask, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return solve<float>(TFMPC_TVLQR_MODEL(float), x0, states, actions, costs, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        status, mask, workspace, workspace_bytes, stream);
 }
 
 }  // namespace tfmpc
 
 extern "C" {
 
-size_t tfmpc_tvlqr_workspace_bytes(int B, int n, int m, int T)
-{
-    if (B <= 0 || n <= 0 || m <= 0 || T <= 0) return 0;
-    return (size_t)B * T * m * (n + 1) * sizeof(float);
-}
+size_t tfmpc_tvlqr_workspace_bytes(int B, int n, int m, int T) { return workspace_bytes<float>(B, n, m, T); }
+size_t tfmpc_tvlqr_workspace_bytes_f64(int B, int n, int m, int T) { return workspace_bytes<double>(B, n, m, T); }
 
 const char *tfmpc_tvlqr_kernel_name(int n, int m, int T)
 {
     (void)T;
     if (n <= 0 || m <= 0) return "invalid";
     if (tvlqr_mfma_supported(n, m)) return (n == 16 && m == 8) ? "tv_mfma_16x8" : "tv_mfma_16x8 (zero-padded)";
-    if (tvlqr_generic_smem_bytes(n, m) > kMaxLdsBytes) return "unsupported";
+    if (!supported(float(), n, m)) return "unsupported";
     return "tv_generic_wave";
 }
 
-int tfmpc_tvlqr_backward_f32(TFMPC_TVLQR_MODEL_PARAMS, float *K, float *k, float *V, float *v, float *cst,
+const char *tfmpc_tvlqr_kernel_name_f64(int n, int m, int T)
+{
+    (void)T;
+    if (n <= 0 || m <= 0) return "invalid";
+    if (!supported(double(), n, m)) return "unsupported";
+    return tvlqr_f64_kernel_name(n, m);
+}
+
+int tfmpc_tvlqr_backward_f32(TFMPC_TVLQR_MODEL_PARAMS(float), float *K, float *k, float *V, float *v, float *cst,
                              int32_t *status, void *stream)
 {
-    const Model md = TFMPC_TVLQR_MODEL;
-    int rc = check_model(B, n, m, T, md);
-    if (rc != TFMPC_OK || B == 0) return rc;
-    if (B > 0 && (!K || !k)) return TFMPC_ERR_ARG;
-    TvLqrArgs a = make_args(B, n, m, T, md);
-    a.K = K; a.k = k; a.sK = (long)T * m * n; a.sk = (long)T * m;
-    a.V = V; a.v = v; a.cst = cst; a.status = status;
-    return run(a, true, false, stream);
+    return backward<float>(TFMPC_TVLQR_MODEL(float), K, k, V, v, cst, status, stream);
 }
 
-int tfmpc_tvlqr_forward_f32(TFMPC_TVLQR_MODEL_PARAMS, const float *K, long strideK, const float *k, long stride_k,
+int tfmpc_tvlqr_backward_f64(TFMPC_TVLQR_MODEL_PARAMS(double), double *K, double *k, double *V, double *v, double *cst,
+                             int32_t *status, void *stream)
+{
+    return backward<double>(TFMPC_TVLQR_MODEL(double), K, k, V, v, cst, status, stream);
+}
+
+int tfmpc_tvlqr_forward_f32(TFMPC_TVLQR_MODEL_PARAMS(float), const float *K, long strideK, const float *k, long stride_k,
                             const float *x0, float *states, float *actions, float *costs, void *stream)
 {
-    const Model md = TFMPC_TVLQR_MODEL;
-    int rc = check_model(B, n, m, T, md);
-    if (rc != TFMPC_OK || B == 0) return rc;
-    if (strideK < 0 || stride_k < 0) return TFMPC_ERR_ARG;
-    if (B > 0 && (!x0 || !states || !costs || !K || !k || !actions)) return TFMPC_ERR_ARG;
-    TvLqrArgs a = make_args(B, n, m, T, md);
-    a.x0 = x0;
-    a.K = const_cast<float *>(K); a.k = const_cast<float *>(k); a.sK = strideK; a.sk = stride_k;
-    a.states = states; a.actions = actions; a.costs = costs;
-    return run(a, false, true, stream);
+    return forward<float>(TFMPC_TVLQR_MODEL(float), K, strideK, k, stride_k, x0, states, actions, costs, stream);
 }
 
-int tfmpc_tvlqr_solve_f32(TFMPC_TVLQR_MODEL_PARAMS, const float *x0, float *states, float *actions, float *costs,
+int tfmpc_tvlqr_forward_f64(TFMPC_TVLQR_MODEL_PARAMS(double), const double *K, long strideK, const double *k,
+                            long stride_k, const double *x0, double *states, double *actions, double *costs, void *stream)
+{
+    return forward<double>(TFMPC_TVLQR_MODEL(double), K, strideK, k, stride_k, x0, states, actions, costs, stream);
+}
+
+int tfmpc_tvlqr_solve_f32(TFMPC_TVLQR_MODEL_PARAMS(float), const float *x0, float *states, float *actions, float *costs,
                           float *K, float *k, float *V, float *v, float *cst, int32_t *status,
                           void *workspace, size_t workspace_bytes, void *stream)
 {
-    const Model md = TFMPC_TVLQR_MODEL;
-    int rc = check_model(B, n, m, T, md);
-    if (rc != TFMPC_OK || B == 0) return rc;
-    if (B > 0 && (!x0 || !states || !costs || !actions)) return TFMPC_ERR_ARG;
-    if (B > 0 && (!K || !k)) {
-        // gains are not a requested output: keep them in caller-provided scratch
-        if (!workspace || workspace_bytes < tfmpc_tvlqr_workspace_bytes(B, n, m, T)) return TFMPC_ERR_WORKSPACE;
-        float *w = static_cast<float *>(workspace);
-        if (!K) K = w;
-        if (!k) k = w + (size_t)B * T * m * n;
-    }
-    TvLqrArgs a = make_args(B, n, m, T, md);
-    a.x0 = x0;
-    a.K = K; a.k = k; a.sK = (long)T * m * n; a.sk = (long)T * m;
-    a.V = V; a.v = v; a.cst = cst;
-    a.states = states; a.actions = actions; a.costs = costs; a.status = status;
-    return run(a, true, true, stream);
+    return solve<float>(TFMPC_TVLQR_MODEL(float), x0, states, actions, costs, K, k, V, v, cst, status, nullptr, workspace,
+                        workspace_bytes, stream);
+}
+
+int tfmpc_tvlqr_solve_f64(TFMPC_TVLQR_MODEL_PARAMS(double), const double *x0, double *states, double *actions,
+                          double *costs, double *K, double *k, double *V, double *v, double *cst, int32_t *status,
+                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    return solve<double>(TFMPC_TVLQR_MODEL(double), x0, states, actions, costs, K, k, V, v, cst, status, nullptr,
+                         workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// tvlqr_kernels.h -- internal launch interface of the time-varying LQR kernels (tvlqr_mfma16x8.hip,
-// tvlqr_generic.hip) and their C-ABI dispatcher (tvlqr_dispatch.hip).  Not installed; the public contract
-// is the TV-LQR block of include/tfmpc_hip.h.
+// tvlqr_kernels.h -- internal launch interface of the time-varying LQR kernels (tvlqr_mfma16x8.hip; tvlqr_generic.hip
+// and tvlqr_f64.hip, the fp32 and double instantiations of tvlqr_wave.h's one body) and their C-ABI dispatcher
+// (tvlqr_dispatch.hip, both precisions).  Not installed; the public contract is the TV-LQR block of
+// include/tfmpc_hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,22 +13,25 @@
 namespace tfmpc {
 
 // Model operand X of instance b at step t starts at X + b * sX_b + t * sX_t (elements; 0 = shared / constant).
-struct TvLqrArgs {
+template <class S>
+struct TvLqrArgsT {
     int B, n, m, T;
-    const float *F, *f, *C, *c;
+    const S *F, *f, *C, *c;
     long sF_b, sF_t, sf_b, sf_t, sC_b, sC_t, sc_b, sc_t;
-    const float *Cfin, *cfin;     // final cost [n][n], [n]; both NULL: C_{T-1}[:n,:n], c_{T-1}[:n]
+    const S *Cfin, *cfin;         // final cost [n][n], [n]; both NULL: C_{T-1}[:n,:n], c_{T-1}[:n]
     long sCfin_b, scfin_b;
-    const float *x0;
-    float *K, *k;                 // [B][T][m][n], [B][T][m]
+    const S *x0;
+    S *K, *k;                     // [B][T][m][n], [B][T][m]
     long sK, sk;                  // batch strides of K, k (forward-only launches may share a policy: 0)
-    float *V, *v, *cst;           // optional value-function outputs [B][T][n][n], [B][T][n], [B][T]
-    float *states, *actions, *costs;
+    S *V, *v, *cst;               // optional value-function outputs [B][T][n][n], [B][T][n], [B][T]
+    S *states, *actions, *costs;
     int32_t *status;
-    const uint32_t *mask;         // [B][T] or NULL; bit i: control i is held at step t (masked sweep)
+    const uint32_t *mask;         // [B][T] or NULL; bit i: control i is held at step t (masked sweep); fp32 only
 };
+using TvLqrArgs = TvLqrArgsT<float>;
 
-__host__ __device__ inline const float *tv_at(const float *p, long sb, long st, int b, int t)
+template <class S>
+__host__ __device__ inline const S *tv_at(const S *p, long sb, long st, int b, int t)
 {
     return p + (size_t)b * sb + (size_t)t * st;
 }
@@ -37,6 +41,11 @@ int tvlqr_mfma_launch(const TvLqrArgs &a, bool backward, bool forward, hipStream
 
 size_t tvlqr_generic_smem_bytes(int n, int m);
 int tvlqr_generic_launch(const TvLqrArgs &a, bool backward, bool forward, hipStream_t stream);
+
+// double precision: n <= 32 and m <= 32; the name is "tv_f64_wave16" or "tv_f64_wave32"
+bool tvlqr_f64_supported(int n, int m);
+const char *tvlqr_f64_kernel_name(int n, int m);
+int tvlqr_f64_launch(const TvLqrArgsT<double> &a, bool backward, bool forward, hipStream_t stream);
 
 // tfmpc_tvlqr_solve_f32 (same arguments, K = k = V = v = cst = NULL) on a MASKED model: for every set bit i of
 // mask[b][t], column n + i of F_t is read as zero, row and column n + i of C_t as zero with a unit diagonal, and

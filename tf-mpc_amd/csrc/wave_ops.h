@@ -83,7 +83,7 @@ __device__ __forceinline__ float quad_xor1(float v) { return dpp_move<kDppQuadXo
 __device__ __forceinline__ float quad_xor2(float v) { return dpp_move<kDppQuadXor2>(0.0f, v); }
 
 // Odd leading dimension: a column walk (stride ld) then touches every LDS bank.
-__host__ __device__ __forceinline__ int odd_ld(int x) { return x | 1; }
+__host__ __device__ constexpr int odd_ld(int x) { return x | 1; }
 
 // out(i, j) = init(i, j) + sum_k a(i, k) * b(k, j), i < M, j < N, wave-cooperative:
 // output elements are dealt round-robin to the 64 lanes.
@@ -245,7 +245,8 @@ __device__ __forceinline__ void fill_nan(float *p, int count)
 }
 
 // Global -> LDS copy of a row-major [rows][cols] matrix into leading dimension ld.
-__device__ __forceinline__ void load_matrix(float *dst, int ld, const float *src, int rows, int cols)
+template <class T>
+__device__ __forceinline__ void load_matrix(T *dst, int ld, const T *src, int rows, int cols)
 {
     wave_for_2d(rows, cols, [&](int r, int c, int idx) { dst[r * ld + c] = src[idx]; });
 }
@@ -264,15 +265,17 @@ __device__ __forceinline__ void store_matrix(float *dst, const float *src, int l
 //                  of tf.linalg.cholesky in ilqr.py:358.  `active` (may be null)
 //                  marks rows that take part; inactive rows/cols must already
 //                  be identity rows (box-QP free/clamped split).
-// fac[rows] and prow[width] are LDS scratch.  Returns 0, or 1 if a pivot was
+// fac[rows] and prow[width] are LDS scratch (prow is unused and may be null).  Returns 0, or 1 if a pivot was
 // zero (PIVOT) / non-positive or NaN (!PIVOT).  All lanes return the same value.
-template <bool PIVOT>
-__device__ __forceinline__ int wave_gauss_jordan(float *aug, int ld, int rows, int width, float *fac, float *prow)
+// T = double (wave_ops_f64.h) is served without pivoting only.
+template <bool PIVOT, class T = float>
+__device__ __forceinline__ int wave_gauss_jordan(T *aug, int ld, int rows, int width, T *fac, T *prow)
 {
     // Column per lane: a lane carries its column(s) j = lane, lane + 64, ... through the whole row sweep of a
     // pivot, so the only cross-lane data are the multipliers fac[i] = aug[i][p] (staged once per pivot, read
     // back as LDS broadcasts) -- no index divisions and two fences per pivot.  Element arithmetic and pivot
     // choice are those of the textbook loop: aug[i][j] <- fma(-aug[i][p], aug[piv][j] / aug[piv][p], aug[i][j]).
+    static_assert(!PIVOT || sizeof(T) == sizeof(float), "the pivot search is fp32 only");
     (void)prow;
     const int lane = lane_id();
     int bad = 0;
@@ -280,7 +283,7 @@ __device__ __forceinline__ int wave_gauss_jordan(float *aug, int ld, int rows, i
         for (int i = lane; i < rows; i += kWave) fac[i] = aug[i * ld + p];
         wsync();
         int piv = p;
-        if (PIVOT) {
+        if constexpr (PIVOT) {
             if (rows <= kWave) {
                 // first row of maximal |entry| among rows p..rows-1, as the sequential scan finds it
                 const bool in = lane >= p && lane < rows;
@@ -296,18 +299,18 @@ __device__ __forceinline__ int wave_gauss_jordan(float *aug, int ld, int rows, i
                 }
             }
         }
-        const float pv = fac[piv];
-        if (PIVOT ? (pv == 0.0f) : !(pv > 0.0f)) bad = 1;
-        const float inv = 1.0f / pv;
+        const T pv = fac[piv];
+        if (PIVOT ? (pv == T(0)) : !(pv > T(0))) bad = 1;
+        const T inv = T(1) / pv;
         for (int j = lane; j < width; j += kWave) {
-            const float pr = aug[piv * ld + j] * inv;            // scaled pivot row, this column
+            const T pr = aug[piv * ld + j] * inv;                // scaled pivot row, this column
             if (PIVOT && piv != p) aug[piv * ld + j] = aug[p * ld + j];   // row p moves into slot piv ...
             // (a chunked read-all-then-write-all row loop is faster for 16+ rows but costs the small systems of the
             // iLQR kernels 25 %; the large shapes have the block kernel)
             for (int i = 0; i < rows; ++i) {
-                const float fi = fac[(PIVOT && i == piv) ? p : i];        // ... and keeps its multiplier
-                const float old = aug[i * ld + j];
-                aug[i * ld + j] = (i == p) ? pr : fmaf(-fi, pr, old);
+                const T fi = fac[(PIVOT && i == piv) ? p : i];            // ... and keeps its multiplier
+                const T old = aug[i * ld + j];
+                aug[i * ld + j] = (i == p) ? pr : fma(-fi, pr, old);
             }
         }
         wsync();

@@ -1,5 +1,6 @@
-// wave_ops_f64.h -- the double-precision twins of the wave-per-instance building blocks of wave_ops.h, for
-// tvlqr_f64.hip.  Separate functions, not templates of the fp32 ones: the fp32 kernels' code does not change.
+// wave_ops_f64.h -- what is double-only among the wave-per-instance building blocks: the 64-bit DPP move, the
+// wave_sum and finite overloads built on it, and the f64 matrix-core product.  Everything else (load_matrix,
+// wave_gauss_jordan<false>, wave_for_2d) is wave_ops.h's own template, instantiated with double.
 //
 // Matrix products run on v_mfma_f64_16x16x4_f64.  Its operands are one double per lane, A[l & 15][k = l >> 4] and
 // B[k = l >> 4][l & 15] as the f32 16x16x4 form, but its C/D map is NOT the f32 one: register r of lane l holds
@@ -25,7 +26,7 @@ __device__ __forceinline__ double dpp_move_f64(double v)
 }
 
 // wave_sum of wave_ops.h in double: the same butterfly, the same order of additions; lanes outside a row mask add +0.0
-__device__ __forceinline__ double wave_sum_f64(double v)
+__device__ __forceinline__ double wave_sum(double v)
 {
     v += dpp_move_f64<kDppQuadXor1>(v);
     v += dpp_move_f64<kDppQuadXor2>(v);
@@ -39,7 +40,7 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
-__device__ __forceinline__ bool finite_f64(double x) { return fabs(x) <= DBL_MAX; }
+__device__ __forceinline__ bool finite(double x) { return fabs(x) <= DBL_MAX; }
 
 // out(i, j, init(i, j) + sum_k a(i, k) b(k, j)), i < M, j < N, in 16 x 16 output tiles on v_mfma_f64_16x16x4_f64, one
 // wave.  Rows, columns and k beyond the matrix are ZERO operands (the read itself is clamped into the matrix, so no
@@ -85,38 +86,6 @@ __device__ __forceinline__ void wave_matmul_f64(int M, int N, int K, FA a, FB b,
             }
         }
     }
-}
-
-// Global -> LDS copy of a row-major [rows][cols] matrix of doubles into leading dimension ld.
-__device__ __forceinline__ void load_matrix_f64(double *dst, int ld, const double *src, int rows, int cols)
-{
-    wave_for_2d(rows, cols, [&](int r, int c, int idx) { dst[r * ld + c] = src[idx]; });
-}
-
-// wave_gauss_jordan<false> of wave_ops.h in double: in-place elimination WITHOUT pivoting of aug[rows][width]
-// (leading dimension ld), whose first `rows` columns hold a symmetric matrix; on return columns rows .. width - 1 hold
-// A^-1 RHS.  A column per lane; fac[rows] is LDS scratch.  Returns 1 if a pivot was non-positive or NaN (the matrix
-// is not positive definite), else 0; all lanes return the same value.
-__device__ __forceinline__ int wave_eliminate_f64(double *aug, int ld, int rows, int width, double *fac)
-{
-    const int lane = lane_id();
-    int bad = 0;
-    for (int p = 0; p < rows; ++p) {
-        for (int i = lane; i < rows; i += kWave) fac[i] = aug[i * ld + p];
-        wsync();
-        const double pv = fac[p];
-        if (!(pv > 0.0)) bad = 1;
-        const double inv = 1.0 / pv;
-        for (int j = lane; j < width; j += kWave) {
-            const double pr = aug[p * ld + j] * inv;
-            for (int i = 0; i < rows; ++i) {
-                const double old = aug[i * ld + j];
-                aug[i * ld + j] = (i == p) ? pr : fma(-fac[i], pr, old);
-            }
-        }
-        wsync();
-    }
-    return bad;
 }
 
 }  // namespace tfmpc
