@@ -27,7 +27,8 @@
 //      the backward sweep) -> K~ = -Q_uu^-1 [Q_ux | q_u].  The reference takes a general
 //      inverse (lqr.py:84-87); for a symmetric C with C_uu > 0 (the precondition stated in
 //      include/tfmpc_hip.h) Q_uu is SPD and the two agree to rounding.  A non-positive pivot is
-//      reported in status[b] (TFMPC_ST_NOT_PD / _SINGULAR).
+//      reported in status[b] (TFMPC_ST_NOT_PD / _SINGULAR).  Launches without value outputs run blocks of TWO waves and one of
+//      them eliminates the systems of both instances at once (PAIR below, wave_ldlt8_pair.h): same bits, half the elimination.
 //   4. V' = Q_xx + Q_xu K, v' = q_x + Q_xu k: 4 x v_mfma_f32_16x16x4_f32 (the Schur-complement
 //      form of the four-term update lqr.py:97-105, equal to it in exact arithmetic), then
 //      V' <- (V' + V'^T) / 2 through an LDS transpose: steps 2 and 3 use the symmetry of V, so its
@@ -51,6 +52,7 @@
 #include "options.h"
 #include "mfma_bf16x3.h"
 #include "wave_ldlt8.h"
+#include "wave_ldlt8_pair.h"
 #include "wave_ops.h"
 
 namespace tfmpc {
@@ -155,12 +157,31 @@ typedef float f32x4_any __attribute__((ext_vector_type(4), aligned(4)));
 #define TFMPC_LQR_WAVES(EU_) (EU_)
 #endif
 #define TFMPC_LQR_OCCUPANCY __attribute__((amdgpu_waves_per_eu(TFMPC_LQR_WAVES(EU), TFMPC_LQR_WAVES(EU))))
-template <bool BACKWARD, bool FORWARD, bool VALUE, bool EXACT, bool BF3, bool OUT16 = false, int EU = 4>
-__global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel(LqrArgs a)
+// PAIR (round 9): blocks of TWO waves, instance = 2 blockIdx.x + wave, each wave with its own LDS slice.  Everything is still wave-per-
+// instance EXCEPT the 8 x 8 elimination: per sweep step ONE wave (the solver, alternating with the step's parity so that the two SIMDs
+// share the work) eliminates the systems of both instances at once (wave_ldlt8_pair.h: system A in lanes 0..31, B in lanes 32..63, DPP row
+// broadcasts for pivots and multipliers) between two block barriers.  The elimination's instruction count does not depend on how many
+// columns ride along, so it is paid once per pair.  EVERY path executes the same number of block barriers in both waves: the second wave
+// of an odd last block runs on a clamped instance index with every global store suppressed (`live`), it never exits early.
+// Launches without value outputs only: the VALUE / 16-bit instantiations read q_u and k by v_readlane 24 and keep the one-wave block.
+// Barrier that orders LDS traffic of the block only (what lds_sync() is to one wave): s_waitcnt lgkmcnt(0) + s_barrier, no vmcnt(0).
+__device__ __forceinline__ void block_lds_sync()
 {
-    __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
-    const int b = blockIdx.x;
-    const int lane = threadIdx.x;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+template <bool BACKWARD, bool FORWARD, bool VALUE, bool EXACT, bool BF3, bool OUT16 = false, int EU = 4, bool PAIR = false>
+__global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel(LqrArgs a)
+{
+    static_assert(!PAIR || (BACKWARD && !VALUE && !OUT16), "the paired elimination serves the sweeps without value outputs");
+    __shared__ __attribute__((aligned(16))) float lds_all[(PAIR ? 2 : 1) * kLdsFloats];
+    const int wave = PAIR ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
+    float *const lds = lds_all + wave * kLdsFloats;          // this wave's slice
+    const int b_own = PAIR ? 2 * (int)blockIdx.x + wave : (int)blockIdx.x;
+    const bool live = !PAIR || b_own < a.B;                  // false: the idle second wave of an odd last block (stores nothing)
+    const int b = live ? b_own : a.B - 1;
+    const int lane = PAIR ? (int)(threadIdx.x & (kWave - 1)) : (int)threadIdx.x;
     const int i = lane & 15, q = lane >> 4;
     const int T = a.T;
     const int n = EXACT ? N : a.n, m = EXACT ? M : a.m, d = n + m;
@@ -222,10 +243,18 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
         f32x4 Vd = Cd00, vd = vterm;
         float cst = 0.0f;
         int min_pivot_bits = 0x3f800000;     // smallest pivot seen, as float bits (int order == float order for >= 0)
+        int min_pivot_rows = 0x3f800000;     // PAIR: per lane, over the steps THIS wave eliminated (lanes 0..31: instance of wave 0, 32..63: of wave 1)
+        // PAIR: the solver's column of either slice.  Row of 16 lanes r = 0, 1 of system s = lane >> 5: lanes 0..7 hold Q_uu columns 0..7
+        // (lane 0 of row 1: q_u instead), lanes 8..15 the columns 8r .. 8r+7 of Q_ux.  K~ goes back to the same column of the slice.
+        const int pj = lane & 15, prow = (lane >> 4) & 1;
+        const int pcol = pj >= 8 ? pj - 8 + 8 * prow : ((prow && pj == 0) ? N + M : N + pj);
+        const int pair_src = PAIR ? 4 * pinned(((lane >> 5) * kLdsFloats + kMs + pcol * 8) / 4) : 0;       // (a multiple of 4 floats by construction: 16-byte LDS accesses)
+        const int pair_d0 = (lane >> 5) * kLdsFloats + kMs + N * 8;      // Q_uu[0][0] of the lane's system
         constexpr int kZero = kMs + 25 * 8;      // columns 25..31 of the elimination input are never written
         // ... and are the only part of the slice that is read before it is written: column 25 as the zero operand (t01_src, g1_src below), all of
-        // them by the elimination's lanes 25..31 (whose results nobody reads).  q_x overwrites 28, 29 every step; every step writes the columns
-        // 0..24 of the input and ALL of K~ before it reads them, and the transpose staging likewise.
+        // them by the elimination's lanes 25..31 (whose results nobody reads; the paired elimination reads columns 0..24 only).  q_x overwrites
+        // 28, 29 every step; every step writes the columns 0..24 of the input and every column of K~ that is read (PAIR: 0..24, else all)
+        // before it reads them, and the transpose staging likewise.
         if (lane < kKs - kZero) lds[kZero + lane] = 0.0f;
         constexpr int kQx = kMs + 28 * 8;        // q_x staging in pad columns 28, 29
         const int t01_src = (i == M) ? kQx + 4 * q : kZero;
@@ -289,38 +318,59 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
             } else if (q == 2) {
                 lds[kQx + i] = T01t[0];                                                          // q_x[i]
             }
-            lds_sync();
-            // rows (2k, 2k+1) share a register pair so that one v_pk_fma_f32 updates both
-            f32x2 M2[4];
-            {
-                const int c = lane & 31;
-                const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8]);
-                const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8 + 4]);
-                M2[0] = f32x2{lo[0], lo[1]}; M2[1] = f32x2{lo[2], lo[3]};
-                M2[2] = f32x2{hi[0], hi[1]}; M2[3] = f32x2{hi[2], hi[3]};
-            }
             float quk = 0.0f;
-            float qu_saved[8];
-            if (VALUE) {
+            if constexpr (PAIR) {
+                block_lds_sync();            // both slices staged
+                if (wave == (t & 1)) {            // the solver of this step
+                    f32x2 P2[4];
+                    const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds_all[pair_src]);
+                    const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds_all[pair_src + 4]);
+                    const float d0 = lds_all[pair_d0];
+                    P2[0] = f32x2{lo[0], lo[1]}; P2[1] = f32x2{lo[2], lo[3]};
+                    P2[2] = f32x2{hi[0], hi[1]}; P2[3] = f32x2{hi[2], hi[3]};
+                    float Pr[8];
+                    ldlt8_pair_solve_neg(P2, Pr, d0, min_pivot_rows);
+                    // K~ of both slices: columns 0..15 = K, column 24 = k (the copies of Q_uu's lanes land in columns 16..23, which nobody reads)
+                    f32x4 klo, khi;
 #pragma unroll
-                for (int p = 0; p < 8; ++p) qu_saved[p] = readlane(M2[p >> 1][p & 1], 24);
-            }
-            // K~ = -Q_uu^-1 [Q_ux | . | q_u]   (lqr.py:84-87; LDL^T on the upper triangle, wave_ldlt8.h)
-            float Mr[8];
-            ldlt8_solve_neg(M2, Mr, min_pivot_bits);
-            if (VALUE) {
+                    for (int r = 0; r < 4; ++r) { klo[r] = Pr[r]; khi[r] = Pr[4 + r]; }
+                    *reinterpret_cast<f32x4 *>(&lds_all[pair_src + (kKs - kMs)]) = klo;
+                    *reinterpret_cast<f32x4 *>(&lds_all[pair_src + (kKs - kMs) + 4]) = khi;
+                }
+                block_lds_sync();            // both K~ written
+            } else {
+                lds_sync();
+                // rows (2k, 2k+1) share a register pair so that one v_pk_fma_f32 updates both
+                f32x2 M2[4];
+                {
+                    const int c = lane & 31;
+                    const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8]);
+                    const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8 + 4]);
+                    M2[0] = f32x2{lo[0], lo[1]}; M2[1] = f32x2{lo[2], lo[3]};
+                    M2[2] = f32x2{hi[0], hi[1]}; M2[3] = f32x2{hi[2], hi[3]};
+                }
+                float qu_saved[8];
+                if (VALUE) {
 #pragma unroll
-                for (int p = 0; p < 8; ++p) quk = fmaf(readlane(Mr[p], 24), qu_saved[p], quk);   // k^T q_u
-            }
-            // K~: columns 0..15 = K, column 24 = k
-            if (lane < 32) {
-                f32x4 lo, hi;
+                    for (int p = 0; p < 8; ++p) qu_saved[p] = readlane(M2[p >> 1][p & 1], 24);
+                }
+                // K~ = -Q_uu^-1 [Q_ux | . | q_u]   (lqr.py:84-87; LDL^T on the upper triangle, wave_ldlt8.h)
+                float Mr[8];
+                ldlt8_solve_neg(M2, Mr, min_pivot_bits);
+                if (VALUE) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { lo[r] = Mr[r]; hi[r] = Mr[4 + r]; }
-                *reinterpret_cast<f32x4 *>(&lds[kKs + lane * 8]) = lo;
-                *reinterpret_cast<f32x4 *>(&lds[kKs + lane * 8 + 4]) = hi;
+                    for (int p = 0; p < 8; ++p) quk = fmaf(readlane(Mr[p], 24), qu_saved[p], quk);   // k^T q_u
+                }
+                // K~: columns 0..15 = K, column 24 = k
+                if (lane < 32) {
+                    f32x4 lo, hi;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { lo[r] = Mr[r]; hi[r] = Mr[4 + r]; }
+                    *reinterpret_cast<f32x4 *>(&lds[kKs + lane * 8]) = lo;
+                    *reinterpret_cast<f32x4 *>(&lds[kKs + lane * 8 + 4]) = hi;
+                }
+                lds_sync();
             }
-            lds_sync();
             // 4. V' = Q_xx + Q_xu K ; v' = q_x + Q_xu k (column 24)            lqr.py:97-105
             //    contraction over the 8 actions as 2 k-steps: a = 4s + q
             //    vacc accumulates v' on q_x in column 24 (lanes i == 8); every other lane reads its
@@ -353,7 +403,7 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
                 vd = vacc;
             }
             // gains to HBM, row-major K[t][a][j], k[t][a] (the public layout)
-            {
+            if (live) {
                 const int ka = lane >> 3, jc = lane & 7;
                 float2 kv;
                 kv.x = lds[kKs + (2 * jc) * 8 + ka];
@@ -409,6 +459,15 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
         constexpr int kPeeled = VALUE ? 0 : 1;       // the VALUE instantiations store V', v' of every step
         for (int t = T - 1; t >= kPeeled; --t) sweep_step(t, std::false_type{});
         if (kPeeled && T > 0) sweep_step(0, std::true_type{});
+        if constexpr (PAIR) {
+            // each wave holds the pivots of the steps it eliminated, for BOTH instances: exchanged through column 25 of K~ (never read or
+            // written by the paired step), own slice [instance of wave 0, instance of wave 1]
+            constexpr int kMinPv = kKs + 25 * 8;
+            if ((lane & 31) == 0) lds[kMinPv + (lane >> 5)] = __builtin_bit_cast(float, min_pivot_rows);
+            block_lds_sync();
+            const int p0 = __builtin_bit_cast(int, lds_all[kMinPv + wave]), p1 = __builtin_bit_cast(int, lds_all[kLdsFloats + kMinPv + wave]);
+            min_pivot_bits = __builtin_amdgcn_readfirstlane(p0 < p1 ? p0 : p1);
+        }
         if (min_pivot_bits <= 0) status |= (min_pivot_bits == 0) ? TFMPC_ST_SINGULAR : TFMPC_ST_NOT_PD;
         if (VALUE && !(cst == cst)) status |= TFMPC_ST_NAN;
     }
@@ -456,7 +515,7 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
         if (lane < N) {
             const float x = (EXACT || lane < n) ? a.x0[(size_t)b * n + lane] : 0.0f;
             zs[lane] = x;
-            if (EXACT || lane < n) xs[lane] = x;
+            if (live && (EXACT || lane < n)) xs[lane] = x;
         }
         // gains of step t for this lane: K[ka][2jc], K[ka][2jc+1], k[ka]
         // EXACT: one per-lane byte offset each for K and k, fixed for the whole rollout; the (clamped, wave-uniform) step moves an SGPR base
@@ -506,7 +565,7 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
                 }
                 part += __shfl_xor(part, 16, kWave);
                 part += __shfl_xor(part, 32, kWave);
-                if (q == 0 && 16 * nt + i < rows) out[16 * nt + i] = part;
+                if (live && q == 0 && 16 * nt + i < rows) out[16 * nt + i] = part;
             }
         };
 
@@ -564,7 +623,9 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
                 if (tb + d < tc) rollout_step(tb + d, t0 + tb + d, KR[d], kR[d], std::false_type{});
             // chunk epilogue: stage costs on the matrix cores, bulk coalesced stores
             chunk_costs(tc, cs + t0);
-            if (EXACT) {
+            if (!live) {
+                // the idle wave of an odd last block stores nothing
+            } else if (EXACT) {
                 // rows 1..tc of the buffer are x_{t0+1..t0+tc}, rows 0..tc-1 hold u_{t0..t0+tc-1}: every iteration is one LDS read and one
                 // store at immediate offsets from a fixed source and a chunk-uniform destination, the row guard stores exactly tc rows
                 const gbytes xdst = uniform_base(xs + (size_t)(t0 + 1) * N), udst = uniform_base(us + (size_t)t0 * M);
@@ -595,13 +656,13 @@ __global__ __launch_bounds__(kWave) TFMPC_LQR_OCCUPANCY void lqr_mfma16x8_kernel
         lds_sync();
         chunk_costs(1, cs + T);
         lds_sync();
-        if (lane == 0) {
+        if (live && lane == 0) {
             const float fcost = cs[T];
             if (!(fcost == fcost)) status |= TFMPC_ST_NAN;
         }
     }
 
-    if (a.status && lane == 0) a.status[b] = status;
+    if (live && a.status && lane == 0) a.status[b] = status;
 }
 
 // TFMPC_LQR_MFMA=f32 keeps the two big products of the sweep on the f32 MFMA; the default
@@ -624,11 +685,13 @@ int launch_eu(const LqrArgs &a, hipStream_t stream)
 {
     const bool exact = a.n == N && a.m == M;
     const bool bf3 = BW && use_bf16x3();
-    const dim3 grid(a.B), block(kWave);
-    if (exact && bf3) hipLaunchKernelGGL((lqr_mfma16x8_kernel<BW, FW, VAL, true, true, O16, EU>), grid, block, 0, stream, a);
-    else if (exact) hipLaunchKernelGGL((lqr_mfma16x8_kernel<BW, FW, VAL, true, false, O16, EU>), grid, block, 0, stream, a);
-    else if (bf3) hipLaunchKernelGGL((lqr_mfma16x8_kernel<BW, FW, VAL, false, true, O16, EU>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((lqr_mfma16x8_kernel<BW, FW, VAL, false, false, O16, EU>), grid, block, 0, stream, a);
+    // sweeps without value outputs: blocks of two waves that share the elimination (PAIR, see the kernel)
+    constexpr bool P = BW && !VAL && !O16;
+    const dim3 grid(P ? (a.B + 1) / 2 : a.B), block(P ? 2 * kWave : kWave);
+    if (exact && bf3) hipLaunchKernelGGL((lqr_mfma16x8_kernel<BW, FW, VAL, true, true, O16, EU, P>), grid, block, 0, stream, a);
+    else if (exact) hipLaunchKernelGGL((lqr_mfma16x8_kernel<BW, FW, VAL, true, false, O16, EU, P>), grid, block, 0, stream, a);
+    else if (bf3) hipLaunchKernelGGL((lqr_mfma16x8_kernel<BW, FW, VAL, false, true, O16, EU, P>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((lqr_mfma16x8_kernel<BW, FW, VAL, false, false, O16, EU, P>), grid, block, 0, stream, a);
     return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
 }
 
