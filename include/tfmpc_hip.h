@@ -224,7 +224,7 @@ int tfmpc_tvlqr_solve_f32(int B, int n, int m, int T,
  * outputs, statuses, error codes and B == 0 no-op; status stays int32.  One wavefront per instance, the three matrix
  * products of a step on v_mfma_f64_16x16x4_f64, for n <= 32 and m <= 32 (kernel_name_f64: "tv_f64_wave16" for n <= 16
  * and m <= 16, "tv_f64_wave32" otherwise); beyond: TFMPC_ERR_UNSUPPORTED ("unsupported").  The split backward + forward
- * calls give the bits of the fused solve.  workspace_bytes_f64 = B T m (n + 1) 8.  There are no f64 gradient calls. */
+ * calls give the bits of the fused solve.  workspace_bytes_f64 = B T m (n + 1) 8.  Gradients: tfmpc_tvlqr_vjp_f64 below. */
 size_t tfmpc_tvlqr_workspace_bytes_f64(int B, int n, int m, int T);
 const char *tfmpc_tvlqr_kernel_name_f64(int n, int m, int T);
 int tfmpc_tvlqr_backward_f64(int B, int n, int m, int T,
@@ -268,6 +268,34 @@ int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T,
                         float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t,
                         float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
                         float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
+                        int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ----------------------------------- TV-LQR gradients, double precision --------
+ * Vector-Jacobian product of tfmpc_tvlqr_solve_f64: tfmpc_tvlqr_vjp_f32's contract with every value a
+ * double (strides in elements, NULL upstream = zero, a NULL output is not computed, a stride of 0 sums over that axis in a
+ * fixed order without atomics so that repeated calls give identical bits, the default final cost's gradient in dC[T-1],
+ * dc[T-1], dCfin / dcfin without Cfin is TFMPC_ERR_ARG, B == 0 is a no-op, error codes before any launch).  One more
+ * input is REQUIRED: v[B][T][n], the forward solve's value-gradient term (call tfmpc_tvlqr_solve_f64 with v non-NULL).
+ * The costates are the value function's gradient on the optimal trajectory, lam_t = V_t x_t + v_t and
+ * dlam_t = V_t dx_t + v~_t with V, v~ from the adjoint solve: closed-loop, so rounding error does not grow with the
+ * horizon as it does in the f32 call's open-loop costate recursion.  Shapes as the f64 solve serves (n <= 32, m <= 32;
+ * beyond: TFMPC_ERR_UNSUPPORTED).  status[B] (required) gets the adjoint solve's status; an instance with any bit set has
+ * NaN in its own gradient rows and in every batch-summed gradient.  With up(x) = x rounded up to a multiple of 64,
+ * d = n + m and chunks = ceil(B / 256), the workspace holds
+ *   8 * [ up(B T d) + 2 up(B n) + up(B n n) + up(B (T+1) n) + up(B T m) + up(B (T+1)) + up(B T m (n+1))
+ *         + up(B T n n) + up(B T n) + up(2 B T n) + up(chunks T (n d + n + d d + d)) ]  bytes
+ * (fold, adjoint trajectory, the solve's gains, the adjoint's V and v~, the costate records, the partial sums): the V
+ * field alone is 6.7 GB at B = 65536, n = 16, T = 50. */
+size_t tfmpc_tvlqr_vjp_workspace_bytes_f64(int B, int n, int m, int T);
+int tfmpc_tvlqr_vjp_f64(int B, int n, int m, int T,
+                        const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                        const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                        const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                        const double *states, const double *actions, const double *v,
+                        const double *g_states, const double *g_actions, const double *g_costs,
+                        double *dF, long sdF_b, long sdF_t, double *df, long sdf_b, long sdf_t,
+                        double *dC, long sdC_b, long sdC_t, double *dc, long sdc_b, long sdc_t,
+                        double *dCfin, long sdCfin_b, double *dcfin, long sdcfin_b, double *dx0, long sdx0_b,
                         int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------- gradients of the Riccati recursion --------

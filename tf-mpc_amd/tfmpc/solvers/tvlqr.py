@@ -11,7 +11,9 @@ time stride 0 (no copy).  ``C_final`` is ``[n, n]`` or ``[B, n, n]``, ``c_final`
 
 Precision: the default ``dtype=torch.float32`` casts every operand to fp32, float64 inputs included, silently.  Pass
 ``dtype=torch.float64`` for the double-precision kernels (``tfmpc_tvlqr_*_f64``, DESIGN.md 3.14, n <= 32 and m <= 32):
-operands, ``x0`` and every output then stay in double.  Gradients are served in fp32 only.
+operands, ``x0`` and every output then stay in double.  Gradients of the double solve are opt-in:
+``solve(x0, differentiable=True)`` / ``solve_tensors(x0, differentiable=True)`` (``tfmpc_tvlqr_vjp_f64``, DESIGN.md 3.15);
+the Riccati recursion's gradients (``backward(differentiable=True)``) are served in fp32 only.
 """
 
 import numpy as np
@@ -57,7 +59,8 @@ class TimeVaryingLQR:
         ``dtype``: ``torch.float32`` (default) stores fp32 copies of the operands -- float64 inputs are cast down
         silently, as they always were -- and runs the fp32 kernels.  ``torch.float64`` keeps operands, ``x0`` and every
         output in double and runs ``tfmpc_tvlqr_*_f64``; the symmetry check then uses 1e-12 relative in place of 1e-6,
-        and an operand or ``x0`` that requires grad is refused (gradients: ``dtype=torch.float32``)."""
+        and an operand or ``x0`` that requires grad is refused unless the solve is called with ``differentiable=True``
+        (or the problem is built with ``dtype=torch.float32``)."""
         self.dtype = _check_dtype(dtype)
         self._sfx = "f64" if dtype == torch.float64 else "f32"
         self.device = torch.device(device) if device is not None else _hip.default_device()
@@ -109,11 +112,14 @@ class TimeVaryingLQR:
     def _cast(self, a):
         return _as_dtype(a, self.device, self.dtype)
 
-    def _refuse_grad(self, *more):
-        """The double-precision path has no gradient kernels: say so before any launch, never downcast."""
+    def _refuse_grad(self, *more, solve=False):
+        """Double-precision gradients are opt-in (and the Riccati recursion has none): say so before any launch, never
+        downcast."""
         if self.dtype == torch.float64 and tvlqr_grad.wants_grad(*self._sources, *more):
-            raise NotImplementedError("gradients of the time-varying LQR are served in fp32 only: build the problem with "
-                                      "dtype=torch.float32, or detach the operands and x0 for a dtype=torch.float64 solve")
+            how = ("pass differentiable=True to solve / solve_tensors for the double-precision gradients, build the problem "
+                   "with dtype=torch.float32" if solve else "build the problem with dtype=torch.float32")
+            raise NotImplementedError(f"gradients of the time-varying LQR in double are not served by this call: {how}, or "
+                                      "detach the operands and x0 for a dtype=torch.float64 solve")
 
     @staticmethod
     def _vector(t, size, name):
@@ -327,10 +333,10 @@ class TimeVaryingLQR:
             states, actions, costs = states[0], actions[0], costs[0]
         return states, actions, costs
 
-    def solve_device(self, x0, want_policy=False, want_value=False, workspace=None):
+    def solve_device(self, x0, want_policy=False, want_value=False, workspace=None, want_v=False):
         """One kernel launch for ``B`` solves; a dict of device tensors shaped like ``LQR.solve_device``'s
         (``states[B,T+1,n,1]``, ``actions[B,T,m,1]``, ``costs[B,T+1,1,1]``, ``status[B]``, on request
-        ``K, k, V, v, const``).  Never synchronises."""
+        ``K, k, V, v, const``; ``want_v``: ``v`` alone, what the double-precision gradients keep).  Never synchronises."""
         lib = _hip.require_gpu()
         n, m, T = self.state_size, self.action_size, self.horizon
         x0 = self._prep_x0(x0)
@@ -348,6 +354,8 @@ class TimeVaryingLQR:
         if want_value:
             out.update(V=torch.empty((Bk, T, n, n), device=dev, dtype=dt), v=torch.empty((Bk, T, n, 1), device=dev, dtype=dt),
                        const=torch.empty((Bk, T, 1, 1), device=dev, dtype=dt))
+        elif want_v:
+            out.update(v=torch.empty((Bk, T, n, 1), device=dev, dtype=dt))
         ws_bytes = 0
         if not want_policy:
             size = dt.itemsize
@@ -368,13 +376,15 @@ class TimeVaryingLQR:
         out["workspace"] = workspace
         return out
 
-    def solve(self, x0):
+    def solve(self, x0, differentiable=False):
         """A :class:`Trajectory`; with autograd recording and an operand or ``x0`` requiring grad, a
-        :class:`~tfmpc.solvers.tvlqr_grad.TensorTrajectory` differentiable through ``tfmpc_tvlqr_vjp_f32``
-        (``dtype=torch.float64``: ``NotImplementedError`` instead; gradients are fp32 only)."""
-        self._refuse_grad(x0)
+        :class:`~tfmpc.solvers.tvlqr_grad.TensorTrajectory` differentiable through ``tfmpc_tvlqr_vjp_f32``.  With
+        ``dtype=torch.float64`` that needs ``differentiable=True`` (gradients in double through ``tfmpc_tvlqr_vjp_f64``) and
+        is a ``NotImplementedError`` without it; the flag changes nothing for an fp32 problem."""
+        if not differentiable:
+            self._refuse_grad(x0, solve=True)
         if tvlqr_grad.wants_grad(*self._sources, x0):
-            states, actions, costs = self.solve_tensors(x0)
+            states, actions, costs = self.solve_tensors(x0, differentiable)
             return tvlqr_grad.TensorTrajectory(states, actions, costs)
         out = self.solve_device(x0)
         states, actions, costs = out["states"], out["actions"], out["costs"]
@@ -382,11 +392,14 @@ class TimeVaryingLQR:
             states, actions, costs = states[0], actions[0], costs[0]
         return trajectory.Trajectory(states, actions, costs)
 
-    def solve_tensors(self, x0):
+    def solve_tensors(self, x0, differentiable=False):
         """``(states[(B,)T+1,n,1], actions[(B,)T,m,1], costs[(B,)T+1,1,1])`` as tensors; in the autograd graph of the
-        caller's operands and ``x0`` when autograd is recording (gradients: tfmpc/solvers/tvlqr_grad.py; fp32 only,
-        ``dtype=torch.float64`` raises ``NotImplementedError`` there)."""
-        self._refuse_grad(x0)
+        caller's operands and ``x0`` when autograd is recording (gradients: tfmpc/solvers/tvlqr_grad.py).  With
+        ``dtype=torch.float64`` the graph is built only with ``differentiable=True`` (every gradient then fp64, the
+        trajectory the same bits as without grad); without the flag that request raises ``NotImplementedError``."""
+        if not differentiable:
+            self._refuse_grad(x0, solve=True)
+        double = self.dtype == torch.float64
         if not tvlqr_grad.wants_grad(*self._sources, x0):
             out = self.solve_device(x0)
             states, actions, costs = out["states"], out["actions"], out["costs"]
@@ -395,19 +408,20 @@ class TimeVaryingLQR:
             dev = self.device
             src = self._sources
 
-            def op(i, own, shape=None):       # a non-tensor operand needs no grad: its fp32 copy, already shaped
+            def op(i, own, shape=None):       # a non-tensor operand needs no grad: the solver's own copy, already shaped
                 if src[i] is None:
                     return own
-                t = tvlqr_grad.as_f32_graph(src[i], dev)
+                t = tvlqr_grad.as_graph(src[i], dev, self.dtype)
                 return shape(t) if shape else t
             F, C = op(0, self.F), op(2, self.C)
             f = op(1, self.f, lambda t: self._vector(t, n, "f"))
             c = op(3, self.c, lambda t: self._vector(t, d, "c"))
             Cf = op(4, self.C_final)
             cf = op(5, self.c_final, lambda t: t.unsqueeze(-1) if t.dim() == 1 or (t.dim() == 2 and t.shape != (n, 1)) else t)
-            x0g = _as_column(tvlqr_grad.as_f32_graph(x0, dev), n)
-            problem = tvlqr_grad.Problem(lambda x: self.solve_device(x), lambda: self, True, self)
-            states, actions, costs = tvlqr_grad.SolveFunction.apply(problem, x0g, F, f, C, c, Cf, cf)
+            x0g = _as_column(tvlqr_grad.as_graph(x0, dev, self.dtype), n)
+            problem = tvlqr_grad.Problem(lambda x: self.solve_device(x, want_v=double), lambda: self, True, self)
+            function = tvlqr_grad.SolveFunctionF64 if double else tvlqr_grad.SolveFunction
+            states, actions, costs = function.apply(problem, x0g, F, f, C, c, Cf, cf)
         if self._resolve_batch(self._prep_x0(x0.detach() if isinstance(x0, torch.Tensor) else x0)) is None:
             states, actions, costs = states[0], actions[0], costs[0]
         return states, actions, costs

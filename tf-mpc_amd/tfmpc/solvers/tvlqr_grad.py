@@ -1,5 +1,6 @@
 """Differentiable LQR solves: a ``torch.autograd.Function`` over ``tfmpc_tvlqr_solve_f32`` (or ``LQR``'s own solve) and
-``tfmpc_tvlqr_vjp_f32`` (include/tfmpc_hip.h).
+``tfmpc_tvlqr_vjp_f32`` (include/tfmpc_hip.h), and its double-precision twin over
+``tfmpc_tvlqr_solve_f64`` and ``tfmpc_tvlqr_vjp_f64``, which also saves the forward's ``v``.
 
 The backward pass is one more time-varying LQR solve (the adjoint) plus a costate sweep; it needs the forward
 trajectory only, which is what the Function saves.  Each gradient has the shape of its operand: an operand without a
@@ -26,11 +27,16 @@ def wants_grad(*operands):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in operands)
 
 
-def as_f32_graph(a, device):
-    """Like ``lqr._as_f32`` but without ``detach``: a dtype / device conversion stays in the autograd graph."""
+def as_graph(a, device, dtype):
+    """Like ``lqr._as_f32`` / ``tvlqr._as_dtype`` but without ``detach``: a dtype / device conversion stays in the autograd
+    graph."""
     if isinstance(a, torch.Tensor):
-        return a.to(device=device, dtype=torch.float32)
-    return torch.as_tensor(np.asarray(a, dtype=np.float32), device=device)
+        return a.to(device=device, dtype=dtype)
+    return torch.as_tensor(np.asarray(a, dtype=np.float64 if dtype == torch.float64 else np.float32), device=device)
+
+
+def as_f32_graph(a, device):
+    return as_graph(a, device, torch.float32)
 
 
 class Problem:
@@ -55,11 +61,12 @@ def grad_strides(g, ndim_batched, timed):
     return sb, st
 
 
-def alloc_grads(shapes, needed, Bk, device):
-    """One fp32 buffer per operand shape whose gradient is needed, else ``None`` (also for an absent operand, shape
-    ``None``).  Zeros over an empty batch, where no kernel writes."""
+def alloc_grads(shapes, needed, Bk, device, dtype=torch.float32):
+    """One buffer (fp32 by default) per operand shape whose gradient is needed, else ``None`` (also for an absent operand,
+    shape ``None``).  Zeros over an empty batch, where no kernel writes."""
     alloc = torch.zeros if Bk == 0 else torch.empty
-    return [alloc(shape, device=device) if need and shape is not None else None for shape, need in zip(shapes, needed)]
+    return [alloc(shape, device=device, dtype=dtype) if need and shape is not None else None
+            for shape, need in zip(shapes, needed)]
 
 
 class SolveFunction(torch.autograd.Function):
@@ -98,6 +105,47 @@ class SolveFunction(torch.autograd.Function):
                                      *(_hip.ptr(u) for u in ups), *args, _hip.ptr(status), _hip.ptr(ws),
                                      ws.numel() * 4, _hip.stream())
         _hip.check(rc, "tfmpc_tvlqr_vjp_f32")
+        problem.owner.last_grad_status = status
+        return (None, gx0, gF, gf, gC, gc, gCf, gcf)
+
+
+class SolveFunctionF64(torch.autograd.Function):
+    """``SolveFunction`` in double: the forward asks the solve for ``v`` as well (``problem.run`` returns it) and saves
+    it, the backward keeps upstream gradients, gradients and workspace in fp64 and calls ``tfmpc_tvlqr_vjp_f64``."""
+
+    @staticmethod
+    def forward(ctx, problem, x0, F, f, C, c, C_final, c_final):
+        out = problem.run(x0.detach())
+        ctx.problem = problem
+        ctx.meta = [(t.shape if t is not None else None) for t in (x0, F, f, C, c, C_final, c_final)]
+        ctx.save_for_backward(out["states"], out["actions"], out["v"])
+        return out["states"], out["actions"], out["costs"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_states, g_actions, g_costs):
+        states, actions, v = ctx.saved_tensors
+        problem = ctx.problem
+        tv = problem.model()
+        lib = _hip.require_gpu()
+        Bk, T1, n = states.shape[0], states.shape[1], states.shape[2]
+        T, m = T1 - 1, actions.shape[2]
+        dev, f64 = states.device, torch.float64
+        nd_model = 4 if problem.timed else 3
+        gx0, gF, gf, gC, gc, gCf, gcf = alloc_grads(ctx.meta, ctx.needs_input_grad[1:], Bk, dev, f64)
+        args = []
+        for g in (gF, gf, gC, gc):
+            args += [_hip.ptr(g), *grad_strides(g, nd_model, problem.timed)]
+        for g in (gCf, gcf, gx0):
+            args += [_hip.ptr(g), grad_strides(g, 3, False)[0]]
+        ups = [None if g is None else g.to(f64).contiguous() for g in (g_states, g_actions, g_costs)]
+        status = torch.zeros((Bk,), dtype=torch.int32, device=dev)
+        ws_bytes = int(lib.tfmpc_tvlqr_vjp_workspace_bytes_f64(Bk, n, m, T))
+        ws = torch.empty((max(ws_bytes, 8) + 7) // 8, dtype=f64, device=dev)
+        rc = lib.tfmpc_tvlqr_vjp_f64(Bk, n, m, T, *tv._model_args(), _hip.ptr(states), _hip.ptr(actions), _hip.ptr(v),
+                                     *(_hip.ptr(u) for u in ups), *args, _hip.ptr(status), _hip.ptr(ws),
+                                     ws.numel() * 8, _hip.stream())
+        _hip.check(rc, "tfmpc_tvlqr_vjp_f64")
         problem.owner.last_grad_status = status
         return (None, gx0, gF, gf, gC, gc, gCf, gcf)
 
@@ -148,14 +196,15 @@ class TensorTrajectory(trajectory.Trajectory):
         self.detached().save(filepath)
 
 
-def tvlqr_solve(F, f, C, c, x0, C_final=None, c_final=None):
+def tvlqr_solve(F, f, C, c, x0, C_final=None, c_final=None, dtype=torch.float32):
     """Solve the time-varying LQR of :class:`tfmpc.solvers.TimeVaryingLQR` (same operand shapes) from ``x0`` and
     return ``(states, actions, costs)`` as tensors -- ``states[(B,)T+1,n,1]``, ``actions[(B,)T,m,1]``,
-    ``costs[(B,)T+1,1,1]`` -- differentiable with respect to every tensor operand and ``x0`` that requires grad."""
+    ``costs[(B,)T+1,1,1]`` -- differentiable with respect to every tensor operand and ``x0`` that requires grad.
+    ``dtype=torch.float64``: the double-precision solve (n <= 32, m <= 32), outputs and every gradient in fp64."""
     from tfmpc.solvers.tvlqr import TimeVaryingLQR
     device = next((t.device for t in (F, f, C, c, x0) if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
-    tv = TimeVaryingLQR(F, f, C, c, C_final, c_final, device=device)
-    return tv.solve_tensors(x0)
+    tv = TimeVaryingLQR(F, f, C, c, C_final, c_final, device=device, dtype=dtype)
+    return tv.solve_tensors(x0, differentiable=True)
 
 
-__all__ = ["SolveFunction", "TensorTrajectory", "tvlqr_solve"]
+__all__ = ["SolveFunction", "SolveFunctionF64", "TensorTrajectory", "tvlqr_solve"]
