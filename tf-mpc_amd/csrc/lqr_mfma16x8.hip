@@ -74,17 +74,27 @@ __device__ __forceinline__ float readlane(float v, int lane)
 
 using namespace bf3;      // bf16x3 product helpers (mfma_bf16x3.h)
 
-// per-wave LDS slice (floats)
+// per-wave LDS slice (floats).  The sweep and the rollout never use it at the same time, so they OVERLAY each other from float 0 and the slice
+// is the larger of the two (5 536 B: twelve two-wave blocks fit a CU's 160 KB, where the two laid end to end, 7 584 B, let in ten).
+// The __syncthreads() between sweep and rollout orders the two uses: every LDS access of the sweep -- the exchange of the smallest pivots
+// included, which is the last time a wave of a paired block touches its PARTNER's slice -- has completed in both waves before either
+// writes a rollout row.  Backward-only and forward-only launches use one of the two layouts alone.
+//   sweep
 constexpr int kMs = 0;          // [32 cols][8 rows]  elimination input, column-major
 constexpr int kKs = 256;        // [32 cols][8 rows]  K~ = -Q_uu^-1 [Q_ux | . | q_u], column-major
-constexpr int kZs = 512;        // rollout chunk: rows z_t = [x_t(16); u_t(8)], stride kZld (sweep: V' transpose staging)
+constexpr int kVt = 512;        // V' transpose staging [16 cols][kVtLd]
+constexpr int kVtLd = 20;
+constexpr int kSweepFloats = kVt + 16 * kVtLd;
+//   rollout
+constexpr int kZs = 0;          // rollout chunk: rows z_t = [x_t(16); u_t(8)], stride kZld
 constexpr int kZld = 26;        // even (8-byte aligned rows), 26 n mod 32 distinct for n < 16
-constexpr int kVtLd = 20;        // V' transpose staging [16 cols][kVtLd] inside the rollout buffer
 #ifndef TFMPC_LQR_TC
 #define TFMPC_LQR_TC 52
 #endif
 constexpr int kTC = TFMPC_LQR_TC;         // timesteps per rollout chunk (T = 50 fits one chunk of 52)
-constexpr int kLdsFloats = kZs + (kTC + 1) * kZld + 6;
+constexpr int kRolloutFloats = kZs + (kTC + 1) * kZld + 6;
+constexpr int kLdsFloats = kSweepFloats > kRolloutFloats ? kSweepFloats : kRolloutFloats;
+static_assert(kLdsFloats % 4 == 0, "slices are 16-byte aligned (pair_src, the 16-byte accesses of the sweep)");
 #ifndef TFMPC_LQR_RING
 #define TFMPC_LQR_RING 4
 #endif
@@ -142,15 +152,16 @@ typedef float f32x4_any __attribute__((ext_vector_type(4), aligned(4)));
 // OUT16: the 16-bit copies of the policy / value outputs (LqrArgs::K16 ...) are compiled into separate instantiations, so
 // that the default kernels carry none of their code
 // Register budget (round 4).  Left to itself the compiler takes 105 - 109 VGPRs for the solve kernels: FOUR waves per SIMD (512 / 112).  Sized
-// for FIVE (<= 96) the kernels without value-function outputs need 74 - 89 registers and spill nothing -- the LDS slice (7.6 KB) lets 21 waves
-// into a CU -- and the headline launch gains 2 - 4 % on every box tried (tools/probes/r4_headline_eu.sh, alternating: 1.787 -> 1.744 ms, 1.86 ->
+// for FIVE (<= 96) the kernels without value-function outputs need 74 - 89 registers and spill nothing -- the LDS slice (7.6 KB then, 5 536 B since the rollout
+// overlays the sweep: 29 waves of a CU) is not what limits them -- and the headline launch gains 2 - 4 % on every box tried (tools/probes/r4_headline_eu.sh, alternating: 1.787 -> 1.744 ms, 1.86 ->
 // 1.83 ms).  The VALUE instantiations would spill 2 - 19 registers at that budget and keep four.  -DTFMPC_LQR_EU=n forces a budget (A/B builds).
-// Round 5: the budget is a template parameter (EU = resident waves per SIMD the register allocation is sized for) and TFMPC_LQR_WAVES=4|5
+// Round 5: the budget is a template parameter (EU = resident waves per SIMD the register allocation is sized for) and TFMPC_LQR_WAVES=4|5|6
 // picks the instantiation at run time, because round 4's verdict suspected the shard sizes of a strong-scaling run to prefer four: 8 192
 // instances (the 8-GPU shard of the headline batch) are 8 waves per SIMD = 5 + 3 at five resident, 4 + 4 at four.  Measured on every shard
 // size from 1 024 to 65 536 instances (tools/probes/r5_headline_shard_sweep.py, profiles/r05_headline_shard_sweep.json): FIVE wins at each
 // of them (8 192: 0.238 against 0.258 ms; the kernel's time is 27.2 us per wave of a SIMD + ~20 us, the rounds overlap because waves do not
-// finish together), so five stays the rule for every launch.  Same instruction stream per wave up to register allocation: bit-identical.
+// finish together), so five stayed the rule for every launch; six (round 10) is for the paired kernels,
+// whose waves wait for each other.  Same instruction stream per wave up to register allocation: bit-identical.
 #ifdef TFMPC_LQR_EU
 #define TFMPC_LQR_WAVES(EU_) TFMPC_LQR_EU
 #else
@@ -261,7 +272,7 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
         const int g1_src = (i == M) ? kKs + (N + M) * 8 + q : kZero + q;
         // loop-invariant addresses of the step (pinned: see above)
         const int g0_src = pinned(kKs + i * 8 + q);                  // K[4s+q][i]
-        const int vt_dst = pinned(kZs + 4 * q * kVtLd + i);          // V' transpose staging, element [row 4q][column i]
+        const int vt_dst = pinned(kVt + 4 * q * kVtLd + i);          // V' transpose staging, element [row 4q][column i]
         unsigned offK = 8u * lane, offk = 4u * lane;                 // byte offsets of this lane's gains inside a step (EXACT)
         __syncthreads();
 
@@ -392,7 +403,7 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 // Stored element by element as [row 4q+r][column i] (conflict-free: 80 q + i covers the 64 banks once) and read back as ONE
                 // 16-byte row segment [row i][4q .. 4q+3] = V'^T, which lands in a register quad that pairs with T00 for the packed adds.
                 {
-                    const float *vt = &lds[kZs];              // rollout buffer, idle during the sweep
+                    const float *vt = &lds[kVt];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) lds[vt_dst + r * kVtLd] = T00[r];
                     lds_sync();
@@ -472,7 +483,13 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
         if (VALUE && !(cst == cst)) status |= TFMPC_ST_NAN;
     }
 
+    // The rollout takes its lane maps from a copy of the lane index the compiler cannot see through: shared with the sweep's they would stay
+    // alive across it, and at the budget of six waves the sweep has no register to spare for them.  `lane`, `i` and `q` are re-declared ON
+    // PURPOSE inside the rollout's block and shadow the sweep's: everything in that block, code added later included, must bind to these.
+    // (It changes the register allocation of every fused instantiation, not only the six-wave ones; their counts are in the r10 note.)
+    const int lane_rollout = (BACKWARD && FORWARD) ? pinned(lane) : lane;
     if (FORWARD) {
+        const int lane = lane_rollout, i = lane & 15, q = lane >> 4;
         // ---- resident operands of the rollout ------------------------------------------
         const int fi = lane >> 2, fc = lane & 3;       // F: row fi, columns 6fc..6fc+5
         const int ka = lane >> 3, jc = lane & 7;       // K: row ka, columns 2jc, 2jc+1
@@ -672,12 +689,13 @@ bool use_bf16x3()
     return !option_is(kOptLqrMfma, "f32");
 }
 
-// Register budget of a launch without value outputs: five waves per SIMD (see the note above the kernel); TFMPC_LQR_WAVES=4|5 forces
-// (A/B timing, the bit-identity test).
+// Register budget of a launch without value outputs: five waves per SIMD (see the note above the kernel); TFMPC_LQR_WAVES=4|5|6 forces
+// (A/B timing, the bit-identity tests).  Six is served by the paired kernels only (80 VGPRs; the slice of 5 536 B lets twelve two-wave
+// blocks into a CU) and stays an option until it has won the alternating runs by the project's bar (profiles/r10_mfma16x8_budget.md).
 int pick_eu()
 {
     const int forced = option_int(kOptLqrWaves, 0);
-    return forced == 4 ? 4 : 5;
+    return forced == 4 || forced == 6 ? forced : 5;
 }
 
 template <bool BW, bool FW, bool VAL, bool O16, int EU>
@@ -700,7 +718,12 @@ int launch(const LqrArgs &a, hipStream_t stream)
 {
     // the VALUE instantiations would spill at the budget for five (round 4): they keep four
     if constexpr (!VAL) {
-        if (pick_eu() == 5) return launch_eu<BW, FW, VAL, O16, 5>(a, stream);
+        const int eu = pick_eu();
+        // six: the paired kernels only (their waves wait for each other, and a sixth covers the waiters); the others keep five
+        if constexpr (BW && !O16) {
+            if (eu == 6) return launch_eu<BW, FW, VAL, O16, 6>(a, stream);
+        }
+        if (eu >= 5) return launch_eu<BW, FW, VAL, O16, 5>(a, stream);
     }
     return launch_eu<BW, FW, VAL, O16, 4>(a, stream);
 }
