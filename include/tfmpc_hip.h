@@ -374,6 +374,18 @@ int tfmpc_lqr_steady_state_f32(int B, int n, int m,
                                float *K, float *k, float *P, float *p,
                                int32_t *iterations, int32_t *status, void *stream);
 
+/* tfmpc_lqr_steady_state_f32 in double: the same algorithm, argument rules, status bits and NaN
+ * outputs, every operand and output double, products on the f64 matrix cores.  tol = 0.0 selects 4 DBL_EPSILON.
+ * n <= 16, m <= 16: "ss_f64_wave16"; n <= 32, m <= 32: "ss_f64_wave32" (116 KiB of dynamic LDS, one wave per CU);
+ * beyond: TFMPC_ERR_UNSUPPORTED.  No workspace, no atomics. */
+const char *tfmpc_lqr_steady_state_kernel_name_f64(int n, int m);
+int tfmpc_lqr_steady_state_f64(int B, int n, int m,
+                               const double *F, long sF_b, const double *f, long sf_b,
+                               const double *C, long sC_b, const double *c, long sc_b,
+                               int max_iter, double tol,
+                               double *K, double *k, double *P, double *p,
+                               int32_t *iterations, int32_t *status, void *stream);
+
 /* Vector-Jacobian product of tfmpc_lqr_steady_state_f32: given the forward's K[B][m][n], k[B][m],
  * P[B][n][n], p[B][n] and status[B] (fwd_status), and upstream gradients gK, gk, gP, gp of the same per-instance layout
  * (each NULL = zero), writes the gradients of <gK, K> + <gk, k> + <gP, P> + <gp, p> with respect to F, f, C, c.  Model

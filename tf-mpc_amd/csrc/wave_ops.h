@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
+#include <limits>
 
 namespace tfmpc {
 
@@ -77,6 +78,37 @@ __device__ __forceinline__ float wave_max(float v)
     step(__builtin_amdgcn_update_dpp((int)u, (int)u, kDppRowBcast31, 0xC, 0xF, false));
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane((int)u, 63));
 }
+
+// wave_max in double, for NON-NEGATIVE, non-NaN values: their IEEE order is the unsigned order of the
+// 64-bit patterns.  The same six DPP steps, each moving the two halves of the value; a lane that a step does not
+// write keeps its own value.
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ unsigned long long dpp_max_u64(unsigned long long u)
+{
+    const int lo = (int)(unsigned)u, hi = (int)(unsigned)(u >> 32);
+    const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xF, false);
+    const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xF, false);
+    const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
+    return u > o ? u : o;
+}
+
+__device__ __forceinline__ double wave_max(double v)
+{
+    unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    u = dpp_max_u64<kDppQuadXor1>(u);
+    u = dpp_max_u64<kDppQuadXor2>(u);
+    u = dpp_max_u64<kDppRowHalfMirror>(u);
+    u = dpp_max_u64<kDppRowMirror>(u);
+    u = dpp_max_u64<kDppRowBcast15, 0xA>(u);
+    u = dpp_max_u64<kDppRowBcast31, 0xC>(u);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 63);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// |x| for either precision (the pivot search of wave_gauss_jordan)
+__device__ __forceinline__ float wave_abs(float x) { return fabsf(x); }
+__device__ __forceinline__ double wave_abs(double x) { return fabs(x); }
 
 // sum / exchange over groups of 2 or 4 adjacent lanes (a quad)
 __device__ __forceinline__ float quad_xor1(float v) { return dpp_move<kDppQuadXor1>(0.0f, v); }
@@ -213,24 +245,25 @@ __device__ __forceinline__ void wave_for_2d(int rows, int cols, F f)
 }
 
 // X <- (X + X') / 2 in place, X an n x n block with leading dimension ld; the pair (i, j), (j, i) belongs to one lane
-__device__ __forceinline__ void symmetrise(float *X, int ld, int n)
+template <class T>
+__device__ __forceinline__ void symmetrise(T *X, int ld, int n)
 {
     wave_for_2d(n, n, [&](int i, int j, int) {
         if (i < j) {
-            const float s = 0.5f * (X[i * ld + j] + X[j * ld + i]);
+            const T s = T(0.5) * (X[i * ld + j] + X[j * ld + i]);
             X[i * ld + j] = s;
             X[j * ld + i] = s;
         }
     });
 }
 
-// out(i, sum_k a(i, k) x(k)), i < rows, a row per lane: s = 0, then s = fmaf(a(i, k), x(k), s) for k = 0 .. K - 1
-template <class FA, class FX, class FOut>
+// out(i, sum_k a(i, k) x(k)), i < rows, a row per lane: s = 0, then s = fma(a(i, k), x(k), s) for k = 0 .. K - 1
+template <class T = float, class FA, class FX, class FOut>
 __device__ __forceinline__ void wave_matvec(int rows, int K, FA a, FX x, FOut out)
 {
     for (int i = lane_id(); i < rows; i += kWave) {
-        float s = 0.0f;
-        for (int k = 0; k < K; ++k) s = fmaf(a(i, k), x(k), s);
+        T s = T(0);
+        for (int k = 0; k < K; ++k) s = fma(a(i, k), x(k), s);
         out(i, s);
     }
 }
@@ -238,9 +271,10 @@ __device__ __forceinline__ void wave_matvec(int rows, int K, FA a, FX x, FOut ou
 __device__ __forceinline__ bool finite(float x) { return fabsf(x) <= FLT_MAX; }
 
 // quiet NaN into p[0 .. count): the outputs of a flagged instance
-__device__ __forceinline__ void fill_nan(float *p, int count)
+template <class T>
+__device__ __forceinline__ void fill_nan(T *p, int count)
 {
-    const float qnan = __builtin_nanf("");
+    const T qnan = std::numeric_limits<T>::quiet_NaN();
     for (int i = lane_id(); i < count; i += kWave) p[i] = qnan;
 }
 
@@ -251,7 +285,8 @@ __device__ __forceinline__ void load_matrix(T *dst, int ld, const T *src, int ro
     wave_for_2d(rows, cols, [&](int r, int c, int idx) { dst[r * ld + c] = src[idx]; });
 }
 
-__device__ __forceinline__ void store_matrix(float *dst, const float *src, int ld, int rows, int cols)
+template <class T>
+__device__ __forceinline__ void store_matrix(T *dst, const T *src, int ld, int rows, int cols)
 {
     wave_for_2d(rows, cols, [&](int r, int c, int idx) { dst[idx] = src[r * ld + c]; });
 }
@@ -267,7 +302,6 @@ __device__ __forceinline__ void store_matrix(float *dst, const float *src, int l
 //                  be identity rows (box-QP free/clamped split).
 // fac[rows] and prow[width] are LDS scratch (prow is unused and may be null).  Returns 0, or 1 if a pivot was
 // zero (PIVOT) / non-positive or NaN (!PIVOT).  All lanes return the same value.
-// T = double (wave_ops_f64.h) is served without pivoting only.
 template <bool PIVOT, class T = float>
 __device__ __forceinline__ int wave_gauss_jordan(T *aug, int ld, int rows, int width, T *fac, T *prow)
 {
@@ -275,7 +309,6 @@ __device__ __forceinline__ int wave_gauss_jordan(T *aug, int ld, int rows, int w
     // pivot, so the only cross-lane data are the multipliers fac[i] = aug[i][p] (staged once per pivot, read
     // back as LDS broadcasts) -- no index divisions and two fences per pivot.  Element arithmetic and pivot
     // choice are those of the textbook loop: aug[i][j] <- fma(-aug[i][p], aug[piv][j] / aug[piv][p], aug[i][j]).
-    static_assert(!PIVOT || sizeof(T) == sizeof(float), "the pivot search is fp32 only");
     (void)prow;
     const int lane = lane_id();
     int bad = 0;
@@ -287,14 +320,14 @@ __device__ __forceinline__ int wave_gauss_jordan(T *aug, int ld, int rows, int w
             if (rows <= kWave) {
                 // first row of maximal |entry| among rows p..rows-1, as the sequential scan finds it
                 const bool in = lane >= p && lane < rows;
-                const float mine = in ? fabsf(fac[lane]) : 0.0f;
-                const float best = wave_max(mine);
+                const T mine = in ? wave_abs(fac[lane]) : T(0);
+                const T best = wave_max(mine);
                 const unsigned long long hit = __ballot(in && mine == best);
                 if (hit) piv = __ffsll((long long)hit) - 1;
             } else {
-                float best = fabsf(fac[p]);
+                T best = wave_abs(fac[p]);
                 for (int i = p + 1; i < rows; ++i) {
-                    const float a = fabsf(fac[i]);
+                    const T a = wave_abs(fac[i]);
                     if (a > best) { best = a; piv = i; }
                 }
             }

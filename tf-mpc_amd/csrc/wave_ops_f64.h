@@ -1,6 +1,7 @@
 // wave_ops_f64.h -- what is double-only among the wave-per-instance building blocks: the 64-bit DPP move, the
 // wave_sum and finite overloads built on it, and the f64 matrix-core product.  Everything else (load_matrix,
-// wave_gauss_jordan<false>, wave_for_2d) is wave_ops.h's own template, instantiated with double.
+// wave_gauss_jordan, symmetrise, wave_matvec, wave_for_2d) is wave_ops.h's own template, instantiated with double;
+// wave_max(double) is defined there too, ahead of the pivot search that calls it.
 //
 // Matrix products run on v_mfma_f64_16x16x4_f64.  Its operands are one double per lane, A[l & 15][k = l >> 4] and
 // B[k = l >> 4][l & 15] as the f32 16x16x4 form, but its C/D map is NOT the f32 one: register r of lane l holds

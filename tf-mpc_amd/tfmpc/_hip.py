@@ -77,6 +77,9 @@ _SIGNATURES.update({
     # B n m, F f C c (+ batch strides), max_iter tol, K k P p, iterations status stream
     "tfmpc_lqr_steady_state_f32": (_I, [_I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _I, ctypes.c_float,
                                         _P, _P, _P, _P, _P, _P, _P]),
+    "tfmpc_lqr_steady_state_kernel_name_f64": (ctypes.c_char_p, [_I, _I]),
+    "tfmpc_lqr_steady_state_f64": (_I, [_I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _I, ctypes.c_double,
+                                        _P, _P, _P, _P, _P, _P, _P]),
     "tfmpc_lqr_steady_state_vjp_workspace_bytes": (_Z, [_I, _I, _I]),
     "tfmpc_lqr_steady_state_vjp_kernel_name": (ctypes.c_char_p, [_I, _I]),
     # B n m, F f C c (+ batch strides), K k P p fwd_status, gK gk gP gp, max_iter tol, dF df dC dc (+ batch strides),

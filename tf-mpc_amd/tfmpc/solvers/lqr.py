@@ -73,11 +73,102 @@ def _as_f32(a, device):
     return torch.as_tensor(np.asarray(a, dtype=np.float32), device=device)
 
 
+def _as_f64(a, device):
+    """The caller's operand in double, with no pass through fp32."""
+    if isinstance(a, torch.Tensor):
+        return a.detach().to(device=device, dtype=torch.float64)
+    return torch.as_tensor(np.asarray(a, dtype=np.float64), device=device)
+
+
 def _as_column(t, size):
     """``[..., size]`` -> ``[..., size, 1]``; column vectors pass through."""
     if t.dim() >= 2 and t.shape[-1] == 1 and t.shape[-2] == size:
         return t
     return t.unsqueeze(-1)
+
+
+def _model_shapes(F, f, C, c):
+    """Checks the shapes of converted operands; returns ``f, c`` as columns and the batch size (None: un-batched)."""
+    n, d = F.shape[-2], F.shape[-1]
+    f, c = _as_column(f, n), _as_column(c, d)
+    if not (0 < n < d):
+        raise ValueError(f"F must be [n, n+m] with m > 0, got {tuple(F.shape)}")
+    for name, t, shape in (("f", f, (n, 1)), ("C", C, (d, d)), ("c", c, (d, 1))):
+        if tuple(t.shape[-2:]) != shape:
+            raise ValueError(f"{name} must end in shape {shape}, got {tuple(t.shape)}")
+    batches = {t.shape[0] for t, nd in ((F, 3), (f, 3), (C, 3), (c, 3)) if t.dim() == nd}
+    if any(t.dim() not in (2, 3) for t in (F, f, C, c)) or len(batches) > 1:
+        raise ValueError("F, f, C, c take at most one leading batch axis of a common size")
+    return f, c, (batches.pop() if batches else None)
+
+
+def _steady_state_limits(max_iter, tol, n, m):
+    """``max_iter``, ``tol`` as the C ABI takes them (0 / 0.0: the kernel's defaults), after the front end's checks."""
+    if max_iter is None:
+        max_iter = 0
+    elif int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
+    if tol is None:
+        tol = 0.0
+    elif not (np.isfinite(tol) and tol > 0):
+        raise ValueError(f"tol must be a positive finite number, got {tol!r}")
+    if n > 32 or m > 32:
+        raise ValueError(f"the steady-state kernels serve n <= 32 and m <= 32, got n={n}, m={m}")
+    return int(max_iter), float(tol)
+
+
+def _steady_state_dtype(dtype):
+    if dtype not in (None, torch.float32, torch.float64):
+        raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype!r}")
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+_NO_F64_GRAD = ("gradients of the steady state are fp32 only: detach the operands (or call under torch.no_grad()) for "
+                "dtype=torch.float64, or use the fp32 steady_state(differentiable=True)")
+
+
+def _steady_state_launch_f64(F, f, C, c, batch_size, max_iter, tol):
+    """One tfmpc_lqr_steady_state_f64 launch on contiguous double operands of checked shapes: batched
+    ``K, k, P, p, iterations, status``."""
+    n, m = F.shape[-2], F.shape[-1] - F.shape[-2]
+    lib = _hip.require_gpu()
+    Bk = batch_size if batch_size is not None else 1
+    dev, dt = F.device, torch.float64
+    K = torch.empty((Bk, m, n), device=dev, dtype=dt)
+    k = torch.empty((Bk, m, 1), device=dev, dtype=dt)
+    P = torch.empty((Bk, n, n), device=dev, dtype=dt)
+    p = torch.empty((Bk, n, 1), device=dev, dtype=dt)
+    iterations = torch.zeros((Bk,), dtype=torch.int32, device=dev)
+    status = torch.zeros((Bk,), dtype=torch.int32, device=dev)
+    args = []
+    for t in (F, f, C, c):
+        args += [_hip.ptr(t), t.stride(0) if t.dim() == 3 else 0]
+    rc = lib.tfmpc_lqr_steady_state_f64(Bk, n, m, *args, int(max_iter), float(tol),
+                                        _hip.ptr(K), _hip.ptr(k), _hip.ptr(P), _hip.ptr(p),
+                                        _hip.ptr(iterations), _hip.ptr(status), _hip.stream())
+    _hip.check(rc, "tfmpc_lqr_steady_state_f64")
+    return K, k, P, p, iterations, status
+
+
+def steady_state_f64(F, f, C, c, max_iter=None, tol=None, device=None):
+    """The double-precision steady state of the caller's operands (``tfmpc_lqr_steady_state_f64``):
+    tensors or numpy arrays of any dtype are taken to float64 directly, never through fp32.  Returns a
+    :class:`SteadyState` of float64 tensors (``iterations``, ``status`` int32).  ``C`` must be symmetric to 1e-12 of its
+    largest entry.  Gradients are not served in double: an operand that requires grad while autograd is recording
+    raises ``NotImplementedError``."""
+    if tvlqr_grad.wants_grad(*(a for a in (F, f, C, c) if isinstance(a, torch.Tensor))):
+        raise NotImplementedError(_NO_F64_GRAD)
+    device = torch.device(device) if device is not None else _hip.default_device()
+    F, f, C, c = (_as_f64(a, device) for a in (F, f, C, c))
+    f, c, batch_size = _model_shapes(F, f, C, c)
+    if C.numel() and not bool((C - C.transpose(-1, -2)).abs().amax() <= 1e-12 * C.abs().amax()):
+        raise NotImplementedError("the steady state is served for a symmetric C only")
+    n, m = F.shape[-2], F.shape[-1] - F.shape[-2]
+    max_iter, tol = _steady_state_limits(max_iter, tol, n, m)
+    outs = _steady_state_launch_f64(*(t.contiguous() for t in (F, f, C, c)), batch_size, max_iter, tol)
+    if batch_size is None:
+        outs = tuple(t[0] for t in outs)
+    return SteadyState(*outs)
 
 
 class LQR:
@@ -92,18 +183,8 @@ class LQR:
         self._sources = tuple(a if isinstance(a, torch.Tensor) else None for a in (F, f, C, c))
         self.last_grad_status = None
         F, f, C, c = (_as_f32(a, self.device) for a in (F, f, C, c))
-        n, d = F.shape[-2], F.shape[-1]
-        f, c = _as_column(f, n), _as_column(c, d)
-        if not (0 < n < d):
-            raise ValueError(f"F must be [n, n+m] with m > 0, got {tuple(F.shape)}")
-        for name, t, shape in (("f", f, (n, 1)), ("C", C, (d, d)), ("c", c, (d, 1))):
-            if tuple(t.shape[-2:]) != shape:
-                raise ValueError(f"{name} must end in shape {shape}, got {tuple(t.shape)}")
-        batches = {t.shape[0] for t, nd in ((F, 3), (f, 3), (C, 3), (c, 3)) if t.dim() == nd}
-        if any(t.dim() not in (2, 3) for t in (F, f, C, c)) or len(batches) > 1:
-            raise ValueError("F, f, C, c take at most one leading batch axis of a common size")
+        f, c, self.batch_size = _model_shapes(F, f, C, c)
         self.F, self.f, self.C, self.c = (t.contiguous() for t in (F, f, C, c))
-        self.batch_size = batches.pop() if batches else None
         self.last_status = None
         # asymmetry beyond fp32 rounding of a symmetric matrix -> the reference's term-by-term recursion
         if symmetric is not None:
@@ -330,8 +411,8 @@ class LQR:
             states, actions, costs = states[0], actions[0], costs[0]
         return states, actions, costs
 
-    # -- infinite horizon (tfmpc_lqr_steady_state_f32) --------------
-    def steady_state(self, max_iter=None, tol=None, differentiable=False):
+    # -- infinite horizon (tfmpc_lqr_steady_state_f32 / _f64) ---
+    def steady_state(self, max_iter=None, tol=None, differentiable=False, dtype=None):
         """The stationary solution of this problem: the limits of ``backward(T)``'s ``K_0, k_0, V_0, v_0`` as T grows,
         found by the structure-preserving doubling algorithm in one kernel launch.  ``max_iter`` caps the doubling steps
         (default 40), ``tol`` is the relative change of P at which it stops (default 4 fp32 ulps).  Returns a
@@ -341,26 +422,30 @@ class LQR:
         ``differentiable=True``: when autograd is recording and a tensor operand requires grad, ``K, k, P, p`` are in the
         autograd graph, with gradients from ``tfmpc_lqr_steady_state_vjp_f32`` (tfmpc/solvers/steady_state_grad.py,
         DESIGN.md 3.10); the backward pass's per-instance status goes to ``last_grad_status``.  The outputs are the same
-        bits as without grad."""
+        bits as without grad.
+
+        ``dtype``: ``None`` or ``torch.float32`` is the fp32 kernel.  ``torch.float64`` upcasts the operands this solver
+        STORES, which are fp32, and returns the double solution of that fp32-rounded problem as float64 tensors
+        (``tfmpc_lqr_steady_state_f64``; ``tol`` then defaults to 4 double ulps): the terminal cost for
+        ``TimeVaryingLQR.from_lqr(lqr, T, ss.P, ss.p, dtype=torch.float64)``.  For operands that are double to begin
+        with, use ``tfmpc.solvers.lqr_steady_state(..., dtype=torch.float64)``.  Gradients are fp32 only: with
+        ``torch.float64``, ``differentiable=True`` or an operand that requires grad raises ``NotImplementedError``."""
+        double = _steady_state_dtype(dtype) == torch.float64
         if not self.symmetric_cost:
             raise NotImplementedError("the steady state is served for a symmetric C only")
         grad = tvlqr_grad.wants_grad(*self._sources)
+        if double and (grad or differentiable):
+            raise NotImplementedError(_NO_F64_GRAD)
         if grad and not differentiable:
             raise NotImplementedError("gradients through the steady state are served with steady_state(differentiable=True) "
                                       "or tfmpc.solvers.lqr_steady_state: otherwise call it under torch.no_grad() or with "
                                       "operands that do not require grad")
-        if max_iter is None:
-            max_iter = 0
-        elif int(max_iter) != max_iter or int(max_iter) < 1:
-            raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
-        if tol is None:
-            tol = 0.0
-        elif not (np.isfinite(tol) and tol > 0):
-            raise ValueError(f"tol must be a positive finite number, got {tol!r}")
-        n, m = self.state_size, self.action_size
-        if n > 32 or m > 32:
-            raise ValueError(f"the steady-state kernels serve n <= 32 and m <= 32, got n={n}, m={m}")
-        if grad:
+        max_iter, tol = _steady_state_limits(max_iter, tol, self.state_size, self.action_size)
+        if double:
+            outs = _steady_state_launch_f64(*(t.to(torch.float64) for t in (self.F, self.f, self.C, self.c)),
+                                            self.batch_size, max_iter, tol)
+            self.last_status = outs[-1]
+        elif grad:
             from tfmpc.solvers import steady_state_grad
             outs = steady_state_grad.SteadyStateFunction.apply(self, int(max_iter), float(tol),
                                                                *steady_state_grad.graph_operands(self))

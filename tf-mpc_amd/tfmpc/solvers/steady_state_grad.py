@@ -73,13 +73,20 @@ class SteadyStateFunction(torch.autograd.Function):
         return (None, None, None, *grads)
 
 
-def lqr_steady_state(F, f, C, c, max_iter=None, tol=None):
+def lqr_steady_state(F, f, C, c, max_iter=None, tol=None, dtype=None):
     """The stationary solution of the LQR ``(F, f, C, c)`` (operand shapes as :class:`tfmpc.solvers.lqr.LQR`) as a
     :class:`~tfmpc.solvers.lqr.SteadyState` whose ``K, k, P, p`` are differentiable with respect to every tensor operand
     that requires grad.  ``max_iter`` and ``tol`` as :meth:`LQR.steady_state`; they also bound the backward's Stein
-    solve."""
-    from tfmpc.solvers.lqr import LQR
+    solve.
+
+    ``dtype=torch.float64`` keeps the caller's operands (tensors, or numpy arrays through ``np.float64``) in double, with
+    no pass through fp32, and returns float64 tensors from ``tfmpc_lqr_steady_state_f64``; ``C`` must
+    then be symmetric to 1e-12 relative, and an operand that requires grad raises ``NotImplementedError`` (gradients
+    are fp32 only).  ``None`` or ``torch.float32`` is the fp32 path."""
+    from tfmpc.solvers.lqr import LQR, _steady_state_dtype, steady_state_f64
     device = next((t.device for t in (F, f, C, c) if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
+    if _steady_state_dtype(dtype) == torch.float64:
+        return steady_state_f64(F, f, C, c, max_iter, tol, device=device)
     return LQR(F, f, C, c, device=device).steady_state(max_iter, tol, differentiable=True)
 
 

@@ -9,7 +9,10 @@
 
 Instances are a pool of 512 distinct draws, instance b holding its own copy of pool[b % 512].  Prints one JSON object
 (median / min of --reps timed launches after --warmup).
-Usage: python tools/lqr_steady_state_rate.py [--reps 20] [--warmup 3] [--out file.json]"""
+
+--dtype float64 times tfmpc_lqr_steady_state_f64 on workloads (a) and (b), the operands upcast once
+outside the timed region, with the fp32 kernel timed in the same run beside it; (c) and (d) are left out.
+Usage: python tools/lqr_steady_state_rate.py [--dtype float32|float64] [--reps 20] [--warmup 3] [--out file.json]"""
 import argparse
 import json
 import os
@@ -26,6 +29,7 @@ for p in (ROOT, os.path.join(ROOT, "tf-mpc_amd"), os.path.join(ROOT, "tests")):
 
 import lqr_steady_state_ref as ssref  # noqa: E402
 from tfmpc import _hip  # noqa: E402
+from tfmpc.solvers import lqr as lqr_module  # noqa: E402
 from tfmpc.solvers.lqr import LQR  # noqa: E402
 
 B, N, M, POOL = 65536, 16, 8, 512
@@ -97,6 +101,31 @@ def line(name, pool, reps, warmup, sample=16):
     }
 
 
+def line_f64(name, pool, reps, warmup, sample=16):
+    """The double kernel and, in the same run, the fp32 kernel on the same (fp32-rounded) problems."""
+    F, f, C, c = pool
+    idx = np.arange(B) % POOL
+    lqr = LQR(F[idx], f[idx], C[idx], c[idx], device="cuda", symmetric=True)
+    ops = [t.to(torch.float64) for t in (lqr.F, lqr.f, lqr.C, lqr.c)]
+    launch = lambda: lqr_module._steady_state_launch_f64(*ops, B, 0, 0.0)      # noqa: E731
+    K64, _, _, _, its, status = launch()
+    ss32 = lqr.steady_state()
+    torch.cuda.synchronize()
+    its, status, its32 = its.cpu().numpy(), status.cpu().numpy(), ss32.iterations.cpu().numpy()
+    K64, K32 = K64[:sample].cpu().numpy(), ss32.K[:sample].cpu().numpy()
+    med32, min32 = timed(lambda: lqr.steady_state(), reps, warmup)
+    med64, min64 = timed(launch, reps, warmup)
+    refs = [ssref.steady_state(F[b], f[b], C[b], c[b])["K"] for b in range(sample)]
+    return {
+        f"{name}_f64_ms": med64, f"{name}_f64_min_ms": min64, f"{name}_f32_ms": med32, f"{name}_f32_min_ms": min32,
+        f"{name}_f64_over_f32": med64 / med32, f"{name}_f64_flagged": int((status != 0).sum()),
+        f"{name}_f64_iterations_median": float(np.median(its)), f"{name}_f64_iterations_max": int(its.max()),
+        f"{name}_f32_iterations_median": float(np.median(its32)),
+        f"{name}_f64_gain_rel_error_median": float(np.median([gain_error(K64[b], refs[b]) for b in range(sample)])),
+        f"{name}_f32_gain_rel_error_median": float(np.median([gain_error(K32[b], refs[b]) for b in range(sample)])),
+    }
+
+
 def scipy_per_instance(pool, count=64):
     import scipy.linalg
     from threadpoolctl import threadpool_limits
@@ -121,11 +150,24 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out")
+    ap.add_argument("--dtype", choices=("float32", "float64"), default="float32")
     args = ap.parse_args()
     _hip.require_gpu()
     torch.cuda.set_device(0)
     a = ssref.make_lqr_batch(N, M, POOL, seed=0)
     d = ssref.damped_workload(N, M, POOL, seed=0)
+    if args.dtype == "float64":
+        out = {"B": B, "n": N, "m": M, "reps": args.reps, "device": torch.cuda.get_device_name(0),
+               "kernel": _hip.load().tfmpc_lqr_steady_state_kernel_name_f64(N, M).decode(),
+               "kernel_f32": _hip.load().tfmpc_lqr_steady_state_kernel_name(N, M).decode()}
+        out.update(line_f64("a_make_lqr", a, args.reps, args.warmup))
+        out.update(line_f64("b_damped", d, args.reps, args.warmup))
+        text = json.dumps(out)
+        print(text)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(text + "\n")
+        return
     out = {"B": B, "n": N, "m": M, "kernel": _hip.load().tfmpc_lqr_steady_state_kernel_name(N, M).decode(), "reps": args.reps}
     out.update(line("a_make_lqr", a, args.reps, args.warmup))
     out.update(line("b_damped", d, args.reps, args.warmup))
