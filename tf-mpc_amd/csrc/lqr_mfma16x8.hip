@@ -37,8 +37,8 @@
 //   K_t, k_t stream to HBM (row-major, the public K/k layout) for the rollout.
 // Forward rollout (lqr.py:141-155): wave-wide fp32 FMA mat-vecs with F rows resident in
 //   registers, z_t = [x_t; u_t] staged in LDS, K_t prefetched one step ahead, DPP reductions;
-//   the stage costs are priced afterwards as C Z on the matrix cores, states / actions leave in
-//   bulk coalesced stores.
+//   the stage costs are priced afterwards as C Z on the matrix cores, sixteen steps per tile -- the final cost rides in the last
+//   chunk's tiles as one more row with a zeroed action part -- and states / actions leave in bulk coalesced stores.
 //
 // The f32 MFMA is an exact fp32 FMA chain (MI355X_MICROARCH.md) and bf16x3 drops only terms below
 // 2^-24 relative, so numerics are those of fp32 VALU code with a different summation order.
@@ -483,11 +483,12 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
         if (VALUE && !(cst == cst)) status |= TFMPC_ST_NAN;
     }
 
-    // The rollout takes its lane maps from a copy of the lane index the compiler cannot see through: shared with the sweep's they would stay
-    // alive across it, and at the budget of six waves the sweep has no register to spare for them.  `lane`, `i` and `q` are re-declared ON
-    // PURPOSE inside the rollout's block and shadow the sweep's: everything in that block, code added later included, must bind to these.
-    // (It changes the register allocation of every fused instantiation, not only the six-wave ones; their counts are in the r10 note.)
-    const int lane_rollout = (BACKWARD && FORWARD) ? pinned(lane) : lane;
+    // The rollout takes its lane maps from a lane index of its own, read anew from v_mbcnt (the lane's number inside its wave: what `lane` is in
+    // either block shape) and opaque to the compiler: shared with the sweep's, the maps -- and threadIdx.x itself -- would stay alive across the
+    // sweep, and at the budget of six waves the sweep has no register to spare for them.  `lane`, `i` and `q` are re-declared ON PURPOSE inside
+    // the rollout's block and shadow the sweep's: everything in that block, code added later included, must bind to these.  The status store
+    // at the end of the kernel picks its lane by the same index.  (Register counts: profiles/r11_mfma16x8_budget.md.)
+    const int lane_rollout = (BACKWARD && FORWARD) ? pinned((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))) : lane;
     if (FORWARD) {
         const int lane = lane_rollout, i = lane & 15, q = lane >> 4;
         // ---- resident operands of the rollout ------------------------------------------
@@ -562,8 +563,10 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
         __syncthreads();
 
         // costs of rows [0, rows) of the chunk buffer: 1/2 z^T C z + c^T z  (lqr.py:41-47)
-        // as C Z on the matrix cores, 16 timesteps per tile.
+        // as C Z on the matrix cores, 16 timesteps per tile.  Every cost is computed from its own row alone (column i of the tile), whatever
+        // the other columns hold.  Returns the costs of the LAST tile, row 16 nt + i in the lanes of column i.
         auto chunk_costs = [&](int rows, float *out) {
+            float part = 0.0f;
             for (int nt = 0; nt * 16 < rows; ++nt) {
                 const int row = (16 * nt + i < rows) ? 16 * nt + i : rows - 1;    // stay inside the chunk
                 const float *zrow = zs + row * kZld;
@@ -574,7 +577,7 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                     D0 = mfma(Ca0[s2], bz, D0);
                     D1 = mfma(Ca1[s2], bz, D1);
                 }
-                float part = 0.0f;
+                part = 0.0f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     part = fmaf(zrow[4 * q + r], fmaf(0.5f, D0[r], cq0[r]), part);
@@ -582,8 +585,12 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 }
                 part += __shfl_xor(part, 16, kWave);
                 part += __shfl_xor(part, 32, kWave);
-                if (live && q == 0 && 16 * nt + i < rows) out[16 * nt + i] = part;
+                if (live && q == 0 && 16 * nt + i < rows) {
+                    unsigned offc = 4u * lane;        // (q == 0: lane == i)
+                    gstore(uniform_base(out + 16 * nt), offc, part);
+                }
             }
+            return part;
         };
 
         // One rollout step: row tt of the chunk buffer, step t of the horizon, gains from one slot of the ring.
@@ -624,9 +631,14 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
         const float *xsrc = zs + (1 + xrow) * kZld + 4 * (lane & 3);
         const float *usrc = zs + urow * kZld + N + 4 * (lane & 1);
         unsigned off16 = 16u * lane;
+        // rows of the chunk an iteration of the stores still has ahead of it, opaque to the compiler: it would fold the two tests on it into
+        // one per-lane bound per iteration and keep those in registers across the chunk
+        auto rows_left = [](int v) { asm("" : "+s"(v)); return v; };
 
-        for (int t0 = 0; t0 < T; t0 += kTC) {
-            const int tc = (T - t0 < kTC) ? (T - t0) : kTC;
+        // (T = 0 runs the loop once with no step: its one row is x_0, priced as the final cost)
+        for (int t0 = 0; t0 == 0 || t0 < T; t0 += kTC) {
+            const bool last = T - t0 <= kTC;
+            const int tc = last ? T - t0 : kTC;
             int tb = 0;
             for (; tb + kRing <= tc; tb += kRing) {
 #pragma unroll
@@ -638,8 +650,20 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
 #pragma unroll
             for (int d = 0; d < kRing - 1; ++d)
                 if (tb + d < tc) rollout_step(tb + d, t0 + tb + d, KR[d], kR[d], std::false_type{});
-            // chunk epilogue: stage costs on the matrix cores, bulk coalesced stores
-            chunk_costs(tc, cs + t0);
+            // chunk epilogue: stage costs on the matrix cores, bulk coalesced stores.
+            // The LAST chunk prices the final cost 1/2 x_T^T C_xx x_T + c_x^T x_T == stage cost with u = 0 (lqr.py:49-57) in the same tiles:
+            // row tc of the buffer holds x_T (the last step put it there, or the prologue at T = 0), and its action part -- never written, or a
+            // stale action of an earlier chunk -- is zeroed here.  Nothing else reads those eight floats: the action stores below read rows 0..tc-1.
+            if (last) {
+                if (lane < M) zs[tc * kZld + N + lane] = __builtin_bit_cast(float, pinned(0));     // (a zero made here: one shared with the loop would live across it)
+                lds_sync();
+            }
+            const float tile_costs = chunk_costs(last ? tc + 1 : tc, cs + t0);       // row tc goes to cs[t0 + tc] == cs[T]
+            if (last) {
+                // the final cost as the lane that stored it holds it: nobody reads cs[T] back
+                const float fcost = readlane(tile_costs, tc & 15);
+                if (!(fcost == fcost)) status |= TFMPC_ST_NAN;
+            }
             if (!live) {
                 // the idle wave of an odd last block stores nothing
             } else if (EXACT) {
@@ -648,14 +672,16 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 const gbytes xdst = uniform_base(xs + (size_t)(t0 + 1) * N), udst = uniform_base(us + (size_t)t0 * M);
 #pragma unroll
                 for (int r0 = 0; r0 < kTC; r0 += kWave / 4) {
-                    if (r0 >= tc) break;
-                    if (r0 + xrow < tc)
+                    const int left = rows_left(tc - r0);
+                    if (left <= 0) break;
+                    if (xrow < left)
                         gstore<f32x4_any>(xdst + r0 * (N * 4), off16, *reinterpret_cast<const f32x4_lds *>(xsrc + r0 * kZld));
                 }
 #pragma unroll
                 for (int r0 = 0; r0 < kTC; r0 += kWave / 2) {
-                    if (r0 >= tc) break;
-                    if (r0 + urow < tc)
+                    const int left = rows_left(tc - r0);
+                    if (left <= 0) break;
+                    if (urow < left)
                         gstore<f32x4_any>(udst + r0 * (M * 4), off16, *reinterpret_cast<const f32x4_lds *>(usrc + r0 * kZld));
                 }
             } else {
@@ -664,22 +690,17 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 for (int idx = lane; idx < tc * m; idx += kWave)
                     us[(size_t)t0 * m + idx] = zs[(idx / m) * kZld + N + idx % m];
             }
-            lds_sync();
-            if (lane < N) zs[lane] = zs[tc * kZld + lane];      // carry x into row 0 of the next chunk
-            lds_sync();
-        }
-        // final cost 1/2 x^T C_xx x + c_x^T x == stage cost with u = 0      lqr.py:49-57
-        if (lane < M) zs[N + lane] = 0.0f;
-        lds_sync();
-        chunk_costs(1, cs + T);
-        lds_sync();
-        if (live && lane == 0) {
-            const float fcost = cs[T];
-            if (!(fcost == fcost)) status |= TFMPC_ST_NAN;
+            if (!last) {
+                lds_sync();
+                if (lane < N) zs[lane] = zs[kTC * kZld + lane];      // carry x into row 0 of the next chunk
+                lds_sync();
+            }
         }
     }
 
-    if (live && a.status && lane == 0) a.status[b] = status;
+    // `status` is wave-uniform here: the pivot bits come out of a v_readfirstlane, `cst` is a wave sum, and the final cost's NaN test reads one
+    // lane's value with v_readlane in every lane -- whichever lane stores it stores the same word.
+    if (live && a.status && lane_rollout == 0) a.status[b] = status;
 }
 
 // TFMPC_LQR_MFMA=f32 keeps the two big products of the sweep on the f32 MFMA; the default
@@ -691,7 +712,8 @@ bool use_bf16x3()
 
 // Register budget of a launch without value outputs: five waves per SIMD (see the note above the kernel); TFMPC_LQR_WAVES=4|5|6 forces
 // (A/B timing, the bit-identity tests).  Six is served by the paired kernels only (80 VGPRs; the slice of 5 536 B lets twelve two-wave
-// blocks into a CU) and stays an option until it has won the alternating runs by the project's bar (profiles/r10_mfma16x8_budget.md).
+// blocks into a CU) and stays an option: it has to beat five by the project's bar in every session taken, and against the shortened
+// elimination it no longer does in any (profiles/r10_mfma16x8_budget.md, profiles/r11_mfma16x8_budget.md).
 int pick_eu()
 {
     const int forced = option_int(kOptLqrWaves, 0);
