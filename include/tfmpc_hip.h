@@ -354,6 +354,45 @@ int tfmpc_tvlqr_box_vjp_f32(int B, int n, int m, int T,
                             float *dlow, long sdlow_b, long sdlow_t, float *dhigh, long sdhigh_b, long sdhigh_t,
                             uint32_t *clamp_mask, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------ control-limited TV-LQR, the solve --------
+ * The forward of tfmpc_tvlqr_box_vjp_f32: the optimum of the TV-LQR problem under low <= u_t <= high.
+ * Model operands, Cfin / cfin and their strides as in tfmpc_tvlqr_solve_f32; low, high as in tfmpc_tvlqr_box_vjp_f32
+ * ([m] per (b, t), batch and time strides in elements, +-inf allowed; low <= high is a PRECONDITION).  u_init: [T][m] per
+ * instance with batch stride su_b (0 = shared), NULL = zeros; it is clipped into the box.  The problem is a convex QP with
+ * an exact model (PRECONDITION as the TV-LQR block: C_t symmetric, C_t >= 0, C_t,uu > 0), solved by control-limited Newton
+ * sweeps without regularisation: per pass a backward sweep in delta form around the nominal with a projected-Newton box-QP
+ * per step (warm start 0, at most 100 iterations: TFMPC_ST_QP_MAXITER; the free block eliminated without pivoting, a
+ * non-positive pivot: TFMPC_ST_NOT_PD), then the first of the step sizes 1, 1/2, ..., 2^-10 whose clipped closed-loop
+ * rollout lowers the total cost (taken untested, at most three passes in a row, while the predicted decrease is below
+ * 1e-6 max(1, |J|), the rounding of J).  Stops when max |k_t,i| <= tol max(1, max |u|) (tol = 0: 4e-6), after max_iter
+ * passes (0: 100; TFMPC_ST_MAX_ATTEMPTS), or when no step size lowers the cost.  The sweep that meets the stop rule still
+ * has its step applied, in full and untested (a step of tol left out is several fp32 roundings of the optimum): the total
+ * cost after this last step is NOT checked to have decreased, the step does not count towards the three trusted passes,
+ * and clamp_mask holds the held sets of the sweep that produced it.  status reports the LAST sweep only: a
+ * TFMPC_ST_QP_MAXITER raised in an earlier pass is dropped when a later pass runs.
+ * Outputs: states[B][T+1][n], actions[B][T][m], costs[B][T+1] of the final nominal -- a control on a bound carries the
+ * bound's bits, which is what tfmpc_tvlqr_box_vjp_f32's held-set rule reads; iterations[B], the backward sweeps run (0
+ * when low == high everywhere); status[B]; reason[B] (optional): 0 converged by the step norm, 1 no step size lowered the
+ * cost, 2 the pass cap, 3 flagged; clamp_mask[B][T] (optional): the last sweep's held sets, bit i = control i (zero for
+ * an instance that ran no sweep).  An instance flagged TFMPC_ST_NOT_PD or
+ * TFMPC_ST_NAN gets NaN in its own rows of states, actions and costs and touches nothing else; one flagged
+ * TFMPC_ST_QP_MAXITER or TFMPC_ST_MAX_ATTEMPTS keeps its last feasible nominal.  One wave per instance, no horizon cap, no
+ * atomics; m <= 32 and whatever one wave's LDS holds (n = m = 32 included), TFMPC_ERR_UNSUPPORTED beyond (kernel_name:
+ * "unsupported").  workspace: tfmpc_tvlqr_box_solve_workspace_bytes(B, n, m, T) = 4 B (T m (n + 1) + (T + 1) n + T m + T + 1)
+ * bytes (gains and the candidate trajectory).  Error codes before any launch: TFMPC_ERR_ARG (sizes, max_iter < 0, tol < 0
+ * or NaN, NULL pointers, negative strides), TFMPC_ERR_UNSUPPORTED, TFMPC_ERR_WORKSPACE.  B == 0 is a no-op. */
+size_t tfmpc_tvlqr_box_solve_workspace_bytes(int B, int n, int m, int T);
+const char *tfmpc_tvlqr_box_solve_kernel_name(int n, int m, int T);
+int tfmpc_tvlqr_box_solve_f32(int B, int n, int m, int T,
+                              const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                              const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
+                              const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
+                              const float *low, long slow_b, long slow_t, const float *high, long shigh_b, long shigh_t,
+                              const float *x0, const float *u_init, long su_b, int max_iter, float tol,
+                              float *states, float *actions, float *costs,
+                              int32_t *iterations, int32_t *status, int32_t *reason, uint32_t *clamp_mask,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------- infinite-horizon LQR --------
  * The stationary solution of tfmpc_lqr_*_f32's problem: A = F[:, :n], B = F[:, n:], Q = C_xx,
  * S = C_xu, R = C_uu (C symmetric).  P is the stabilising solution of the discrete algebraic Riccati equation, found by
