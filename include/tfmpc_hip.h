@@ -393,6 +393,27 @@ int tfmpc_tvlqr_box_solve_f32(int B, int n, int m, int T,
                               int32_t *iterations, int32_t *status, int32_t *reason, uint32_t *clamp_mask,
                               void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------ control-limited TV-LQR, the solve in double --------
+ * tfmpc_tvlqr_box_solve_f32 in double precision: the same algorithm, loop caps, status / reason /
+ * iterations / clamp_mask semantics and NaN rows, with every float a double (tol included; strides stay in ELEMENTS).
+ * tol = 0 selects 1e-12; the trusted-step ratio stays 1e-6 and the Armijo constant 1e-4.  Products run on the f64 matrix
+ * cores.  One wave per instance, n <= 32 and m <= 32 (kernel_name: "tv_box_f64_wave16" for n <= 16 and m <= 16,
+ * "tv_box_f64_wave32" otherwise; "unsupported" beyond, "invalid" for n <= 0 or m <= 0), TFMPC_ERR_UNSUPPORTED beyond.
+ * workspace: tfmpc_tvlqr_box_solve_workspace_bytes_f64(B, n, m, T) = 8 B (T m (n + 1) + (T + 1) n + T m + T + 1) bytes, 0
+ * for B <= 0.  The same argument, shape and workspace checks in the same order; B == 0 is a no-op.  A control on a
+ * bound carries the double bound's bits.  There is no double VJP: tfmpc_tvlqr_box_vjp_f32 is the only gradient. */
+size_t tfmpc_tvlqr_box_solve_workspace_bytes_f64(int B, int n, int m, int T);
+const char *tfmpc_tvlqr_box_solve_kernel_name_f64(int n, int m, int T);
+int tfmpc_tvlqr_box_solve_f64(int B, int n, int m, int T,
+                              const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                              const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                              const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                              const double *low, long slow_b, long slow_t, const double *high, long shigh_b, long shigh_t,
+                              const double *x0, const double *u_init, long su_b, int max_iter, double tol,
+                              double *states, double *actions, double *costs,
+                              int32_t *iterations, int32_t *status, int32_t *reason, uint32_t *clamp_mask,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------- infinite-horizon LQR --------
  * The stationary solution of tfmpc_lqr_*_f32's problem: A = F[:, :n], B = F[:, n:], Q = C_xx,
  * S = C_xu, R = C_uu (C symmetric).  P is the stabilising solution of the discrete algebraic Riccati equation, found by

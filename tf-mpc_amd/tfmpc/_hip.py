@@ -73,6 +73,10 @@ _SIGNATURES.update({
     # low high (+ batch, time strides), x0, u_init (+ batch stride), max_iter tol, states actions costs, iterations status
     # reason clamp_mask, workspace workspace_bytes stream
     "tfmpc_tvlqr_box_solve_f32": (_I, _TV_MODEL + [_P, _L, _L] * 2 + [_P, _P, _L, _I, ctypes.c_float] + [_P] * 7 + [_P, _Z, _P]),
+    # ... in double: the same arguments, tol a double
+    "tfmpc_tvlqr_box_solve_workspace_bytes_f64": (_Z, [_I, _I, _I, _I]),
+    "tfmpc_tvlqr_box_solve_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I]),
+    "tfmpc_tvlqr_box_solve_f64": (_I, _TV_MODEL + [_P, _L, _L] * 2 + [_P, _P, _L, _I, ctypes.c_double] + [_P] * 7 + [_P, _Z, _P]),
     "tfmpc_tvlqr_backward_vjp_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "tfmpc_tvlqr_backward_vjp_kernel_name": (ctypes.c_char_p, [_I, _I, _I]),
     # K k V v fwd_status, gK gk gV gv gconst, dF df dC dc (+ batch, time strides), dCfin dcfin (+ batch stride),

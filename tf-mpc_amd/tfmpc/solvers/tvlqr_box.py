@@ -1,5 +1,6 @@
 """Control-limited time-varying LQR: ``tfmpc_tvlqr_box_solve_f32`` (include/tfmpc_hip.h), the forward
-of :func:`tfmpc.solvers.tvlqr_box_vjp`.
+of :func:`tfmpc.solvers.tvlqr_box_vjp`, and its double-precision twin ``tfmpc_tvlqr_box_solve_f64`` (DESIGN.md §3.18,
+``dtype=torch.float64``: n <= 32, no gradients).
 
 The problem of :class:`tfmpc.solvers.TimeVaryingLQR` under ``low <= u_t <= high``: a convex QP with an exact model,
 solved per instance by control-limited Newton sweeps without regularisation.  Models may vary in time and by instance,
@@ -13,7 +14,7 @@ from torch.autograd.function import once_differentiable
 
 from tfmpc import _hip
 from tfmpc.solvers.box_lqr_grad import BoxLQRInfo, BoxLQRResult, tvlqr_box_vjp
-from tfmpc.solvers.tvlqr_grad import as_f32_graph, wants_grad
+from tfmpc.solvers.tvlqr_grad import as_graph, wants_grad
 
 GRAD_NAMES = ("F", "f", "C", "c", "x0", "low", "high", "C_final", "c_final")
 
@@ -60,13 +61,15 @@ def _strided(t, k, batched):
 class _Call:
     """The launch of one ``tvlqr_box_solve`` call: sizes, options and the :class:`BoxLQRInfo` it fills."""
 
-    def __init__(self, B, T, n, m, u_init, max_iter, tol, info, device):
+    def __init__(self, B, T, n, m, u_init, max_iter, tol, info, device, dtype=torch.float32):
         self.B, self.T, self.n, self.m = B, T, n, m
         self.u_init, self.max_iter, self.tol, self.info, self.device = u_init, max_iter, tol, info, device
+        self.dtype = dtype
 
     def launch(self, F, f, C, c, x0, low, high, Cf, cf):
         lib = _hip.require_gpu()
-        B, T, n, m, dev = self.B, self.T, self.n, self.m, self.device
+        B, T, n, m, dev, dt = self.B, self.T, self.n, self.m, self.device, self.dtype
+        double = dt == torch.float64
         keep, model = [], []
         for t, k in ((F, 2), (f, 1), (C, 2), (c, 1)):
             t, sb, st = _strided(t, k, t.dim() == k + 2)
@@ -88,18 +91,21 @@ class _Call:
         u_init = self.u_init
         su = 0 if u_init is None or u_init.dim() == 2 else T * m
         alloc = torch.zeros if B == 0 else torch.empty
-        states = alloc((B, T + 1, n), device=dev)
-        actions = alloc((B, T, m), device=dev)
-        costs = alloc((B, T + 1), device=dev)
+        states = alloc((B, T + 1, n), dtype=dt, device=dev)
+        actions = alloc((B, T, m), dtype=dt, device=dev)
+        costs = alloc((B, T + 1), dtype=dt, device=dev)
         iterations, status, reason = (torch.zeros((B,), dtype=torch.int32, device=dev) for _ in range(3))
         mask = torch.zeros((B, T), dtype=torch.int32, device=dev)
-        ws_bytes = int(lib.tfmpc_tvlqr_box_solve_workspace_bytes(B, n, m, T))
-        ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
-        rc = lib.tfmpc_tvlqr_box_solve_f32(B, n, m, T, *model, *bounds, _hip.ptr(x0), _hip.ptr(u_init), su, self.max_iter,
-                                           self.tol, _hip.ptr(states), _hip.ptr(actions), _hip.ptr(costs),
-                                           _hip.ptr(iterations), _hip.ptr(status), _hip.ptr(reason), _hip.ptr(mask),
-                                           _hip.ptr(ws), ws.numel() * 4, _hip.stream())
-        _hip.check(rc, "tfmpc_tvlqr_box_solve_f32")
+        size = 8 if double else 4
+        query = lib.tfmpc_tvlqr_box_solve_workspace_bytes_f64 if double else lib.tfmpc_tvlqr_box_solve_workspace_bytes
+        solve, name = ((lib.tfmpc_tvlqr_box_solve_f64, "tfmpc_tvlqr_box_solve_f64") if double else
+                       (lib.tfmpc_tvlqr_box_solve_f32, "tfmpc_tvlqr_box_solve_f32"))
+        ws_bytes = int(query(B, n, m, T))
+        ws = torch.empty((max(ws_bytes, size) + size - 1) // size, dtype=dt, device=dev)
+        rc = solve(B, n, m, T, *model, *bounds, _hip.ptr(x0), _hip.ptr(u_init), su, self.max_iter, self.tol,
+                   _hip.ptr(states), _hip.ptr(actions), _hip.ptr(costs), _hip.ptr(iterations), _hip.ptr(status),
+                   _hip.ptr(reason), _hip.ptr(mask), _hip.ptr(ws), ws.numel() * size, _hip.stream())
+        _hip.check(rc, name)
         info = self.info
         info.last_status, info.last_iterations, info.last_reason = status, iterations, reason
         info.last_clamped = (mask.unsqueeze(-1) >> torch.arange(m, device=dev, dtype=torch.int32)) & 1 != 0
@@ -130,7 +136,8 @@ class TvBoxSolveFunction(torch.autograd.Function):
         return (None, *(got[k].reshape(shapes[k].shape) if k in want else None for k in GRAD_NAMES))
 
 
-def tvlqr_box_solve(F, f, C, c, x0, low, high, C_final=None, c_final=None, u_init=None, max_iter=None, tol=None):
+def tvlqr_box_solve(F, f, C, c, x0, low, high, C_final=None, c_final=None, u_init=None, max_iter=None, tol=None,
+                    dtype=None):
     """Solve ``min sum_t 1/2 z_t^T C_t z_t + c_t^T z_t + 1/2 x_T^T C_fin x_T + c_fin^T x_T``, ``x_{t+1} = F_t z_t + f_t``,
     ``low_t <= u_t <= high_t`` from ``x0`` and return ``(states, actions, costs)`` -- ``states[(B,)T+1,n,1]``,
     ``actions[(B,)T,m,1]``, ``costs[(B,)T+1,1,1]`` as :func:`tfmpc.solvers.box_lqr_solve` -- with ``.info``
@@ -151,12 +158,25 @@ def tvlqr_box_solve(F, f, C, c, x0, low, high, C_final=None, c_final=None, u_ini
     When autograd is recording and an operand, a bound or ``x0`` requires grad, the result is in the autograd graph:
     gradients for ``F, f, C, c, x0, low, high, C_final, c_final`` in the operands' own shapes through
     :func:`tfmpc.solvers.tvlqr_box_vjp` on the returned trajectory (once differentiable; exact where the forward
-    converged).  Shape or bound errors (``low > high``, NaN bounds) raise ``ValueError`` before any launch."""
+    converged).  Shape or bound errors (``low > high``, NaN bounds) raise ``ValueError`` before any launch.
+
+    ``dtype``: ``None`` or ``torch.float32`` is the fp32 kernel; float64 inputs are cast to fp32, silently.
+    ``torch.float64`` keeps tensor and numpy operands, bounds, ``x0``, ``u_init`` and the final cost in double, with no
+    pass through fp32, runs ``tfmpc_tvlqr_box_solve_f64`` (n <= 32, ``tol`` defaults to 1e-12) and
+    returns float64 tensors; a held control carries the double bound's bits.  Gradients are fp32 only: with
+    ``torch.float64`` an operand that requires grad raises ``NotImplementedError``."""
+    if dtype not in (None, torch.float32, torch.float64):
+        raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype!r}")
+    dt = torch.float64 if dtype == torch.float64 else torch.float32
     given = (F, f, C, c, x0, low, high, C_final, c_final)
+    if dt == torch.float64 and wants_grad(*given):
+        raise NotImplementedError("gradients of the control-limited time-varying LQR in double are not served: the box VJP "
+                                  "is fp32 only, call with dtype=torch.float32, or detach the operands, bounds and x0 for a "
+                                  "dtype=torch.float64 solve")
     dev = next((t.device for t in given if isinstance(t, torch.Tensor) and t.device.type != "cpu"), _hip.default_device())
     if (C_final is None) != (c_final is None):
         raise ValueError("give both C_final and c_final, or neither")
-    Ft, ft, Ct, ct, xt, lo, hi = (as_f32_graph(a, dev) for a in given[:7])
+    Ft, ft, Ct, ct, xt, lo, hi = (as_graph(a, dev, dt) for a in given[:7])
     if Ft.dim() not in (3, 4):
         raise ValueError(f"F must be [T, n, d] or [B, T, n, d], got {tuple(Ft.shape)}")
     n, d = Ft.shape[-2], Ft.shape[-1]
@@ -169,7 +189,7 @@ def tvlqr_box_solve(F, f, C, c, x0, low, high, C_final=None, c_final=None, u_ini
                low=_bound(lo, m, "low"), high=_bound(hi, m, "high"))
     inner = dict(F=2, f=1, C=2, c=1, low=1, high=1)
     if u_init is not None:
-        u_init = as_f32_graph(u_init, dev).detach()
+        u_init = as_graph(u_init, dev, dt).detach()
         if u_init.dim() >= 3 and u_init.shape[-1] == 1 and u_init.shape[-2] == m:
             u_init = u_init.squeeze(-1)
         if u_init.dim() not in (2, 3) or u_init.shape[-1] != m:
@@ -191,7 +211,7 @@ def tvlqr_box_solve(F, f, C, c, x0, low, high, C_final=None, c_final=None, u_ini
         raise ValueError(f"x0 must be [n], [n, 1], [B, n] or [B, n, 1] with n = {n}, got {tuple(xt.shape)}")
     Cf = cf = None
     if C_final is not None:
-        Cf, cf = as_f32_graph(C_final, dev), as_f32_graph(c_final, dev)
+        Cf, cf = as_graph(C_final, dev, dt), as_graph(c_final, dev, dt)
         if cf.dim() >= 2 and cf.shape[-1] == 1 and cf.shape[-2] == n:
             cf = cf.squeeze(-1)
         if Cf.dim() not in (2, 3) or tuple(Cf.shape[-2:]) != (n, n) or cf.dim() not in (1, 2) or cf.shape[-1] != n:
@@ -231,7 +251,7 @@ def tvlqr_box_solve(F, f, C, c, x0, low, high, C_final=None, c_final=None, u_ini
     info = BoxLQRInfo()
     info.last_reason = None
     info.batched = batched
-    call = _Call(B, T, n, m, u_init, max_iter, tol, info, dev)
+    call = _Call(B, T, n, m, u_init, max_iter, tol, info, dev, dt)
     args = (ops["F"], ops["f"], ops["C"], ops["c"], xt, ops["low"], ops["high"], Cf, cf)
     if wants_grad(*given):
         states, actions, costs = TvBoxSolveFunction.apply(call, *args)
