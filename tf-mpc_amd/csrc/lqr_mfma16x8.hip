@@ -29,8 +29,11 @@
 //      include/tfmpc_hip.h) Q_uu is SPD and the two agree to rounding.  A non-positive pivot is
 //      reported in status[b] (TFMPC_ST_NOT_PD / _SINGULAR).  Launches without value outputs run blocks of TWO waves and one of
 //      them eliminates the systems of both instances at once (PAIR below, wave_ldlt8_pair.h): same bits, half the elimination.
-//   4. V' = Q_xx + Q_xu K, v' = q_x + Q_xu k: 4 x v_mfma_f32_16x16x4_f32 (the Schur-complement
-//      form of the four-term update lqr.py:97-105, equal to it in exact arithmetic), then
+//   4. V' = Q_xx + Q_xu K: 2 x v_mfma_f32_16x16x4_f32 (the Schur-complement form of the four-term update
+//      lqr.py:97-105, equal to it in exact arithmetic).  v' = q_x + Q_xu k is 128 multiply-adds and gets no matrix tile
+//      (a 16 x 16 tile of which one column is used cost two more MFMAs, 64 cycles of the matrix pipe per step): the lanes
+//      of the elimination that hold column j of Q_ux -- and, behind it, of K -- finish v'[j] = q_x[j] + sum_a k[a] Q_ux[a][j]
+//      as ONE chain of eight FMAs, a = 0..7, the same chain in the paired and in the one-wave blocks, and store it over q_x.  Then
 //      V' <- (V' + V'^T) / 2 through an LDS transpose: steps 2 and 3 use the symmetry of V, so its
 //      rounding-level antisymmetric part must not survive a step (it would grow like |F_u K|^2
 //      per step; the reference does not symmetrise, quirk Q6 of SURVEY.md).
@@ -117,6 +120,7 @@ constexpr int kDppHalfMirror = 0x141; // lane i <-> 7 - i inside each 8-lane hal
 // v_lshl_add_u64 per access and step.
 // (The pin hides where the pointer came from, so it is typed as global memory by hand: a generic pointer would be accessed with flat_*.)
 #define TFMPC_GLOBAL __attribute__((address_space(1)))
+#define TFMPC_LDS __attribute__((address_space(3)))      // (likewise for a volatile LDS access: without it, it goes out as flat_*)
 using gbytes = TFMPC_GLOBAL char *;
 __device__ __forceinline__ gbytes uniform_base(const float *p)
 {
@@ -255,21 +259,24 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
         float cst = 0.0f;
         int min_pivot_bits = 0x3f800000;     // smallest pivot seen, as float bits (int order == float order for >= 0)
         int min_pivot_rows = 0x3f800000;     // PAIR: per lane, over the steps THIS wave eliminated (lanes 0..31: instance of wave 0, 32..63: of wave 1)
-        // PAIR: the solver's column of either slice.  Row of 16 lanes r = 0, 1 of system s = lane >> 5: lanes 0..7 hold Q_uu columns 0..7
-        // (lane 0 of row 1: q_u instead), lanes 8..15 the columns 8r .. 8r+7 of Q_ux.  K~ goes back to the same column of the slice.
+        // PAIR: the solver's column of either slice.  Row of 16 lanes r = 0, 1 of system s = lane >> 5: lane 0 holds q_u, lanes 1..7 the
+        // columns 1..7 of Q_uu, lanes 8..15 the columns 8r .. 8r+7 of Q_ux.  K~ goes back to the same column of the slice (column 24 from both rows,
+        // with equal values), and the lanes of Q_ux column j turn q_x[j] into v'[j] in place (pair_qx; step 4).
         const int pj = lane & 15, prow = (lane >> 4) & 1;
-        const int pcol = pj >= 8 ? pj - 8 + 8 * prow : ((prow && pj == 0) ? N + M : N + pj);
+        const int pcol = pj >= 8 ? pj - 8 + 8 * prow : (pj == 0 ? N + M : N + pj);
         const int pair_src = PAIR ? 4 * pinned(((lane >> 5) * kLdsFloats + kMs + pcol * 8) / 4) : 0;       // (a multiple of 4 floats by construction: 16-byte LDS accesses)
         const int pair_d0 = (lane >> 5) * kLdsFloats + kMs + N * 8;      // Q_uu[0][0] of the lane's system
-        constexpr int kZero = kMs + 25 * 8;      // columns 25..31 of the elimination input are never written
-        // ... and are the only part of the slice that is read before it is written: column 25 as the zero operand (t01_src, g1_src below), all of
-        // them by the elimination's lanes 25..31 (whose results nobody reads; the paired elimination reads columns 0..24 only).  q_x overwrites
-        // 28, 29 every step; every step writes the columns 0..24 of the input and every column of K~ that is read (PAIR: 0..24, else all)
-        // before it reads them, and the transpose staging likewise.
+        constexpr int kZero = kMs + 25 * 8;      // columns 25..31 of the elimination input are never written by step 3
+        // ... and are the only part of the slice that is read before it is written: column 25 as the zero operand (t01_src below), all of
+        // them by the elimination's lanes 25..31 (whose results nobody reads; the paired elimination reads columns 0..24 only).  q_x, then v',
+        // overwrites 28, 29 every step, and in a paired launch the solver's Q_uu lanes park their (meaningless) chain results in 30, 31, which
+        // nothing reads there; every step writes the columns 0..24 of the input and every column of K~ that is read (PAIR: 0..15 and 24, else
+        // all) before it reads them, and the transpose staging likewise.  Column 25 stays zero.
         if (lane < kKs - kZero) lds[kZero + lane] = 0.0f;
-        constexpr int kQx = kMs + 28 * 8;        // q_x staging in pad columns 28, 29
+        constexpr int kQx = kMs + 28 * 8;        // q_x staging in pad columns 28, 29; v' takes its place behind the elimination
+        constexpr int kPark = kMs + 30 * 8;      // pad columns 30, 31
+        const int pair_qx = (lane >> 5) * kLdsFloats + (pj >= 8 ? kQx + pj - 8 + 8 * prow : kPark + pj + 8 * prow);
         const int t01_src = (i == M) ? kQx + 4 * q : kZero;
-        const int g1_src = (i == M) ? kKs + (N + M) * 8 + q : kZero + q;
         // loop-invariant addresses of the step (pinned: see above)
         const int g0_src = pinned(kKs + i * 8 + q);                  // K[4s+q][i]
         const int vt_dst = pinned(kVt + 4 * q * kVtLd + i);          // V' transpose staging, element [row 4q][column i]
@@ -337,10 +344,18 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                     const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds_all[pair_src]);
                     const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds_all[pair_src + 4]);
                     const float d0 = lds_all[pair_d0];
+                    // the column once more, for the value chain behind the solve (which overwrites its inputs): read twice -- volatile, or the
+                    // two reads would be merged and the second copy made with eight v_mov_b32 -- rather than read again behind the solve, where
+                    // the partner wave would wait for the round trip
+                    const f32x4 qlo = *(const volatile TFMPC_LDS f32x4 *)&lds_all[pair_src];
+                    const f32x4 qhi = *(const volatile TFMPC_LDS f32x4 *)&lds_all[pair_src + 4];
+                    float vnext = lds_all[pair_qx];                 // q_x[j] in the lanes of Q_ux column j
                     P2[0] = f32x2{lo[0], lo[1]}; P2[1] = f32x2{lo[2], lo[3]};
                     P2[2] = f32x2{hi[0], hi[1]}; P2[3] = f32x2{hi[2], hi[3]};
+                    const float Qc[8] = {qlo[0], qlo[1], qlo[2], qlo[3], qhi[0], qhi[1], qhi[2], qhi[3]};
                     float Pr[8];
-                    ldlt8_pair_solve_neg(P2, Pr, d0, min_pivot_rows);
+                    ldlt8_pair_solve_neg(P2, Pr, d0, min_pivot_rows, Qc, vnext);
+                    lds_all[pair_qx] = vnext;                       // v'[j] = q_x[j] + sum_a k[a] Q_ux[a][j] in place of q_x[j]
                     // K~ of both slices: columns 0..15 = K, column 24 = k (the copies of Q_uu's lanes land in columns 16..23, which nobody reads)
                     f32x4 klo, khi;
 #pragma unroll
@@ -353,13 +368,17 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 lds_sync();
                 // rows (2k, 2k+1) share a register pair so that one v_pk_fma_f32 updates both
                 f32x2 M2[4];
+                float Qc[8];                     // the lane's column as it came in: lanes c < 16 hold Q_ux[0..7][c]
                 {
                     const int c = lane & 31;
                     const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8]);
                     const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8 + 4]);
                     M2[0] = f32x2{lo[0], lo[1]}; M2[1] = f32x2{lo[2], lo[3]};
                     M2[2] = f32x2{hi[0], hi[1]}; M2[3] = f32x2{hi[2], hi[3]};
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { Qc[r] = lo[r]; Qc[4 + r] = hi[r]; }
                 }
+                float vnext = lds[kQx + (lane & 15)];        // q_x[c]
                 float qu_saved[8];
                 if (VALUE) {
 #pragma unroll
@@ -368,9 +387,19 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 // K~ = -Q_uu^-1 [Q_ux | . | q_u]   (lqr.py:84-87; LDL^T on the upper triangle, wave_ldlt8.h)
                 float Mr[8];
                 ldlt8_solve_neg(M2, Mr, min_pivot_bits);
+                float kb[8];                     // k = -Q_uu^-1 q_u (column 24), wave-uniform
+#pragma unroll
+                for (int p = 0; p < 8; ++p) kb[p] = readlane(Mr[p], 24);
                 if (VALUE) {
 #pragma unroll
-                    for (int p = 0; p < 8; ++p) quk = fmaf(readlane(Mr[p], 24), qu_saved[p], quk);   // k^T q_u
+                    for (int p = 0; p < 8; ++p) quk = fmaf(kb[p], qu_saved[p], quk);   // k^T q_u
+                }
+                // v'[c] = q_x[c] + sum_a k[a] Q_ux[a][c] in place of q_x[c]: the chain of the paired solve (wave_ldlt8_pair.h), term for term,
+                // so that both kinds of block give the same bits
+                if constexpr (!decltype(LAST)::value) {
+#pragma unroll
+                    for (int p = 0; p < 8; ++p) vnext = fmaf(kb[p], Qc[p], vnext);
+                    if (lane < N) lds[kQx + lane] = vnext;
                 }
                 // K~: columns 0..15 = K, column 24 = k
                 if (lane < 32) {
@@ -382,19 +411,17 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 }
                 lds_sync();
             }
-            // 4. V' = Q_xx + Q_xu K ; v' = q_x + Q_xu k (column 24)            lqr.py:97-105
-            //    contraction over the 8 actions as 2 k-steps: a = 4s + q
-            //    vacc accumulates v' on q_x in column 24 (lanes i == 8); every other lane reads its
-            //    operands from the always-zero pad columns, so the next v is 0 there.
+            // 4. V' = Q_xx + Q_xu K ; v' = q_x + Q_xu k                        lqr.py:97-105
+            //    V': contraction over the 8 actions as 2 k-steps, a = 4s + q.
+            //    v' was finished by the elimination's lanes (step 3) and stands where q_x stood: lanes i == 8 read their four rows of it,
+            //    every other lane reads the always-zero pad column, so the next v is 0 there.
             if constexpr (!decltype(LAST)::value) {
-                f32x4 vacc = *reinterpret_cast<const f32x4 *>(&lds[t01_src]);
+                const f32x4 vacc = *reinterpret_cast<const f32x4 *>(&lds[t01_src]);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     const float ax = lds[kMs + i * 8 + 4 * s2 + q];            // Q_xu[i][4s+q] = Q_ux[4s+q][i]
                     const float g0 = lds[g0_src + 4 * s2];                     // K[4s+q][i]
-                    const float g1 = lds[g1_src + 4 * s2];                     // K~[4s+q][24] in lanes i == 8
                     T00 = mfma(ax, g0, T00);
-                    vacc = mfma(ax, g1, vacc);
                 }
                 // V' <- (V' + V'^T) / 2 (transpose through LDS).  The elimination above reads only the
                 // upper triangle of Q_uu; that is consistent only while V carries no antisymmetric part

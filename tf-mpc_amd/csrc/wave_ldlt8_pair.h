@@ -1,10 +1,13 @@
 // wave_ldlt8_pair.h -- the 8 x 8 SPD solve of wave_ldlt8.h for TWO independent systems in one wave (lqr_mfma16x8.hip, paired launches).
 // Layout ("one column per lane, eight rows in registers", as there), by rows of 16 lanes:
 //   lanes  0..31: system A,  lanes 32..63: system B;  each system owns two rows of 16 lanes, and in EACH of them
-//   lanes 0..7 of the row: columns 0..7 of Q_uu (every row carries its own copy);  lanes 8..15: eight payload columns.
-// The payload is 17 columns (16 of Q_ux plus q_u): the elimination reads only the upper triangle of Q_uu, so the lane of Q_uu column 0
-// is read for pivot 0 and never again -- the SECOND row of each system keeps q_u there, and every lane takes d_0 = Q_uu[0][0] from the
-// caller (it is an input: a broadcast LDS read ahead of the pivot chain).
+//   lane 0 of the row: q_u;  lanes 1..7: columns 1..7 of Q_uu (every row carries its own copy);  lanes 8..15: eight columns of Q_ux.
+// The payload is 17 columns (16 of Q_ux plus q_u): the elimination reads only the upper triangle of Q_uu, and lane 0 of a row is never a
+// broadcast source (pivot 0 takes d_0 = Q_uu[0][0] from the caller -- it is an input: a broadcast LDS read ahead of the pivot chain -- and
+// every row_newbcast of the solve names a lane >= 1), so a copy of Q_uu column 0 there would be dead weight: lane 0 of BOTH rows keeps
+// q_u instead.  Behind the back substitution lane 0 of every row therefore holds k = -Q_uu^-1 q_u in X[0..7], and lanes 8..15 hold the
+// columns of K next to it: the value update v'[j] = q_x[j] + sum_a k[a] Q_ux[a][j] of the sweep is finished right here, in the lane
+// of column j, as eight v_fmac_f32 whose first source is lane 0's X[a] (the chain at the end of the statement).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,9 +38,12 @@ namespace tfmpc {
 //       previous copy -- so that the 7-p-1 >= 2 updates of the row above lie between copy and first read (rows 5 and 4: all of pivot 7).
 //       Row 6 has one update and broadcasts itself: x_6 was written by pivot 6's v_mul_f32, with pivot 6's update and pivot 7 behind it.
 //   (d) v_rcp_f32_dpp -> v_mul_f32 (transcendental result read by a plain instruction): the v_min_i32(_dpp) of the pivot stands between.
+//   (e) the value chain reads x_0 .. x_7 of lane 0 by DPP, a = 0 first.  x_0 is the LAST row the back substitution writes (its update by
+//       x_1 is the instruction ahead of the chain): `s_nop 1`.  x_1 was last written seven instructions earlier, the others earlier still.
 // Nothing else: inside a group the broadcast register is only read, every update writes a row of its own (forward) or chains through the
 // accumulator (backward: an ordinary interlocked dependence), v_min_i32_dpp's result is read as a plain operand, and the rows x_s a
-// back-substitution row multiplies by are plain operands too.  7 `s_nop 1` and 1 `s_nop 0` in all, none added by the compiler.
+// back-substitution row multiplies by are plain operands too; the value chain runs through its accumulator and its second sources are inputs
+// of the statement.  8 `s_nop 1` and 1 `s_nop 0` in all, none added by the compiler.
 #define TFMPC_BC(L) " row_newbcast:" #L " row_mask:0xf bank_mask:0xf\n\t"
 // pivot p >= 1: ninv = rcp(-d_p) and the smallest pivot, d_p = lane p of the row's own m_p; x_p = m_p * ninv = -row_p / d_p
 #define TFMPC_PIVOT(P) "v_rcp_f32_dpp %[x" #P "], -%[m" #P "]" TFMPC_BC(P) \
@@ -48,6 +54,8 @@ namespace tfmpc {
 // back-substitution update of row p: x_p = fmaf(O[lane s of the row], x_s, x_p), O the copy of the row in the register of m_0 or m_1
 #define TFMPC_BWD(P, O, S) "v_fmac_f32_dpp %[x" #P "], %[" #O "], %[x" #S "]" TFMPC_BC(S)
 #define TFMPC_COPY(O, P) "v_mov_b32 %[" #O "], %[x" #P "]\n\t"
+// value chain, term a: acc = fmaf(x_a[lane 0 of the row] (= k[a]), q_a, acc), q_a = row a of the lane's column AS IT CAME IN
+#define TFMPC_VAL(A) "v_fmac_f32_dpp %[acc], %[x" #A "], %[q" #A "]" TFMPC_BC(0)
 
 // ldlt8_solve_neg (wave_ldlt8.h) with the multipliers per row of 16 lanes.  Every element goes through EXACTLY the chain of fused
 // multiply-adds it goes through there -- the same multiplier, the same operands in the same order, the same rcp(-d) -- so every column comes
@@ -61,7 +69,13 @@ namespace tfmpc {
 //   d0              Q_uu[0][0] of the lane's system (all lanes): pivot 0 takes it from here and uses no broadcast
 //   min_pivot_bits  PER LANE: the smallest pivot seen by the lane's row, as float bits (v_min_i32); the rows of one system agree, those of
 //                   different systems never mix
-__device__ __forceinline__ void ldlt8_pair_solve_neg(const f32x2 (&M2)[4], float (&X)[8], float d0, int &min_pivot_bits)
+//   Q, acc          the value chain: acc = fmaf(k[a], Q[a], acc) for a = 0 .. 7 IN THAT ORDER, k = X[0..7] of lane 0 of the lane's row.  Q is the
+//                   lane's column once more (the solve overwrites M2's copy; registers of their own), acc comes in as q_x[j] in the lane of
+//                   Q_ux column j and goes out as v'[j].  This is the chain of the one-wave blocks (lqr_mfma16x8.hip), term for term.
+//                   (The chain as a statement of its own, which moves the wait for Q's LDS reads behind the solve, costs four register moves
+//                   and was not faster: profiles/r12_mfma16x8_budget.md.)
+__device__ __forceinline__ void ldlt8_pair_solve_neg(const f32x2 (&M2)[4], float (&X)[8], float d0, int &min_pivot_bits, const float (&Q)[8],
+                                                     float &acc)
 {
     float M[8];
 #pragma unroll
@@ -97,11 +111,15 @@ __device__ __forceinline__ void ldlt8_pair_solve_neg(const f32x2 (&M2)[4], float
         TFMPC_COPY(m1, 0)
         TFMPC_BWD(1, m0, 7) TFMPC_BWD(1, m0, 6) TFMPC_BWD(1, m0, 5) TFMPC_BWD(1, m0, 4) TFMPC_BWD(1, m0, 3) TFMPC_BWD(1, m0, 2)
         TFMPC_BWD(0, m1, 7) TFMPC_BWD(0, m1, 6) TFMPC_BWD(0, m1, 5) TFMPC_BWD(0, m1, 4) TFMPC_BWD(0, m1, 3) TFMPC_BWD(0, m1, 2) TFMPC_BWD(0, m1, 1)
+        "s_nop 1\n\t"
+        TFMPC_VAL(0) TFMPC_VAL(1) TFMPC_VAL(2) TFMPC_VAL(3) TFMPC_VAL(4) TFMPC_VAL(5) TFMPC_VAL(6) TFMPC_VAL(7)
         : [x0] "=&v"(X[0]), [x1] "=&v"(X[1]), [x2] "=&v"(X[2]), [x3] "=&v"(X[3]), [x4] "=&v"(X[4]), [x5] "=&v"(X[5]), [x6] "=&v"(X[6]),
           [x7] "=&v"(X[7]), [m0] "+v"(M[0]), [m1] "+v"(M[1]), [m2] "+v"(M[2]), [m3] "+v"(M[3]), [m4] "+v"(M[4]), [m5] "+v"(M[5]),
-          [m6] "+v"(M[6]), [m7] "+v"(M[7]), [mp] "+v"(min_pivot_bits)
-        : [d0] "v"(d0));
+          [m6] "+v"(M[6]), [m7] "+v"(M[7]), [mp] "+v"(min_pivot_bits), [acc] "+v"(acc)
+        : [d0] "v"(d0), [q0] "v"(Q[0]), [q1] "v"(Q[1]), [q2] "v"(Q[2]), [q3] "v"(Q[3]), [q4] "v"(Q[4]), [q5] "v"(Q[5]), [q6] "v"(Q[6]),
+          [q7] "v"(Q[7]));
 }
+#undef TFMPC_VAL
 #undef TFMPC_COPY
 #undef TFMPC_BWD
 #undef TFMPC_FWD
