@@ -70,7 +70,8 @@ int tfmpc_version(void);
  * runs only the vector recursion for k_t, V_x: results agree to fp32 rounding), TFMPC_GROUP_STORED (1 .. 4, default 4: how many step sizes of a
  * line search of the 2 x 2 lane-group kernel keep their candidate trajectory in the workspace; a pass that adopts another one rolls it out once
  * more -- same bits, for tests and A/B timing), TFMPC_BOX_SPECULATE (off | n, default 0: after n rejected passes in a row the helper team of a
- * control-limited instance runs the backward passes of its next passes beside its own -- same bits) are read ONCE per process, at the first use of the library; afterwards only
+ * control-limited instance runs the backward passes of its next passes beside its own -- same bits), TFMPC_TVLQR_TP_PHASES (1 | 2: tfmpc_tvlqr_solve_time_parallel_f64
+ * returns TFMPC_TVLQR_TP_STOPPED (1, not TFMPC_OK) after its condense / its stitch launch and writes no output -- for timing the phases only) are read ONCE per process, at the first use of the library; afterwards only
  * this call changes them (value NULL or "" = back to the dispatcher's own choice).  Returns TFMPC_ERR_ARG
  * for an unknown name.  Process-wide; not meant to be flipped while other threads launch. */
 int tfmpc_set_option(const char *name, const char *value);
@@ -245,6 +246,38 @@ int tfmpc_tvlqr_solve_f64(int B, int n, int m, int T,
                           const double *x0, double *states, double *actions, double *costs,
                           double *K, double *k, double *V, double *v, double *cst, int32_t *status,
                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------- time-varying LQR, double precision, time-parallel --------
+ * tfmpc_tvlqr_solve_f64's problem with the horizon cut into segments that are worked on concurrently:
+ * for a FEW LONG horizons (B <= 64 or so, T in the hundreds or thousands), where one wavefront per instance leaves the
+ * card idle.  `segments` is clamped to T; every segment has len = ceil(T / segments) steps but a shorter last one, and
+ * there are P = ceil(T / len) of them.  Three phases, each one kernel: condense (one wave per instance and segment
+ * reduces its steps to one segment element), stitch (one wave per instance: the value function at every segment's end,
+ * then the state at every segment's start), expand (one wave per instance and segment: tfmpc_tvlqr_solve_f64's own
+ * recursion and rollout on the segment); a fourth, small kernel ORs the status words.  The result is the solution of the
+ * same problem, NOT the bits of tfmpc_tvlqr_solve_f64 (the value function crosses a segment boundary by another formula);
+ * with P == 1 the call forwards to tfmpc_tvlqr_solve_f64 and returns its bits.
+ * Arguments: tfmpc_tvlqr_solve_f64's, with `segments` after `status`; the same operand strides (0 included), final cost,
+ * optional K, k, V, v and the same checks in the same order, then: segments < 1 or cst != NULL is TFMPC_ERR_ARG (the
+ * value function's constant term is not carried through the elements).  The workspace is always required for P > 1:
+ * with w = B P,  8 (w (4 n n + 4 n) + B T m (n + 1)) + the bytes of 2 w + B status words rounded up to 8
+ * (workspace_bytes_f64(B, n, m, T, segments); 0 for an invalid argument); a workspace that is not 8-byte aligned is
+ * TFMPC_ERR_ARG.
+ * status[b] is the OR over the instance's segments and its stitch: TFMPC_ST_NOT_PD for a step's R_t = C_t[n:,n:] or
+ * Q_uu not positive definite, TFMPC_ST_SINGULAR for a singular I + G H at a combine or boundary, TFMPC_ST_NAN as the
+ * sequential solve; a flagged instance has NaN in all its outputs.  No atomics: an instance's bits depend on neither B
+ * nor its position, and repeated calls give identical bits.  kernel_name: "tv_f64_time_parallel16" (n <= 16 and
+ * m <= 16) or "tv_f64_time_parallel32", the sequential kernel's name when P == 1, "unsupported", "invalid". */
+#define TFMPC_TVLQR_TP_STOPPED 1    /* stopped after a phase on request (TFMPC_TVLQR_TP_PHASES): no output was written */
+size_t tfmpc_tvlqr_time_parallel_workspace_bytes_f64(int B, int n, int m, int T, int segments);
+const char *tfmpc_tvlqr_time_parallel_kernel_name_f64(int n, int m, int T, int segments);
+int tfmpc_tvlqr_solve_time_parallel_f64(int B, int n, int m, int T,
+                                        const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                                        const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                                        const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                                        const double *x0, double *states, double *actions, double *costs,
+                                        double *K, double *k, double *V, double *v, double *cst, int32_t *status,
+                                        int segments, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------ TV-LQR gradients --------
  * Vector-Jacobian product of tfmpc_tvlqr_solve_f32: given the forward's states[B][T+1][n] (states[b][0]

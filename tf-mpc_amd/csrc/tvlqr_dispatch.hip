@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "lqr_kernels.h"
+#include "options.h"
 #include "tvlqr_kernels.h"
 
 using namespace tfmpc;
@@ -118,9 +119,32 @@ int solve(int B, int n, int m, int T, const Model<S> &md, const S *x0, S *states
     return launch(a, true, true, static_cast<hipStream_t>(stream));
 }
 
+// The time-parallel solve's segment table: `segments` clamped to T, every segment len = ceil(T / segments) steps but a
+// shorter last one, count = ceil(T / len) of them.
+struct SegmentTable {
+    int len, count;
+};
+SegmentTable segment_table(int T, int segments)
+{
+    if (segments > T) segments = T;
+    const long len = ((long)T + segments - 1) / segments;
+    return {(int)len, (int)((T + len - 1) / len)};
+}
+
+size_t up8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+
+// doubles: the elements, the value function and the state at every segment boundary, the gains; then the status words
+size_t time_parallel_workspace_bytes(int B, int n, int m, int T, int segments)
+{
+    if (B <= 0 || n <= 0 || m <= 0 || T <= 0 || segments < 1) return 0;
+    const size_t w = (size_t)B * segment_table(T, segments).count;
+    return sizeof(double) * (w * (tv_tp_elem_doubles(n) + (size_t)n * n + 2 * n) + (size_t)B * T * m * (n + 1)) +
+           up8(sizeof(int32_t) * (2 * w + B));
+}
+
 }  // namespace
 
-#define TFMPC_TVLQR_MODEL_PARAMS(S)                                                                                     \
+#define TFMPC_TVLQR_MODEL_PARAMS(S)                                                                                    \
     int B, int n, int m, int T, const S *F, long sF_b, long sF_t, const S *f, long sf_b, long sf_t, const S *C, long sC_b, \
         long sC_t, const S *c, long sc_b, long sc_t, const S *Cfin, long sCfin_b, const S *cfin, long scfin_b
 #define TFMPC_TVLQR_MODEL(S) \
@@ -197,6 +221,71 @@ int tfmpc_tvlqr_solve_f64(TFMPC_TVLQR_MODEL_PARAMS(double), const double *x0, do
 {
     return solve<double>(TFMPC_TVLQR_MODEL(double), x0, states, actions, costs, K, k, V, v, cst, status, nullptr,
                          workspace, workspace_bytes, stream);
+}
+
+size_t tfmpc_tvlqr_time_parallel_workspace_bytes_f64(int B, int n, int m, int T, int segments)
+{
+    return time_parallel_workspace_bytes(B, n, m, T, segments);
+}
+
+const char *tfmpc_tvlqr_time_parallel_kernel_name_f64(int n, int m, int T, int segments)
+{
+    if (n <= 0 || m <= 0 || T <= 0 || segments < 1) return "invalid";
+    if (!supported(double(), n, m)) return "unsupported";
+    return segment_table(T, segments).count == 1 ? tvlqr_f64_kernel_name(n, m) : tvlqr_time_parallel_f64_kernel_name(n, m);
+}
+
+int tfmpc_tvlqr_solve_time_parallel_f64(TFMPC_TVLQR_MODEL_PARAMS(double), const double *x0, double *states,
+                                        double *actions, double *costs, double *K, double *k, double *V, double *v,
+                                        double *cst, int32_t *status, int segments, void *workspace,
+                                        size_t workspace_bytes, void *stream)
+{
+    const Model<double> md{F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b};
+    int rc = check_model(B, n, m, T, md);
+    if (rc != TFMPC_OK) return rc;
+    if (segments < 1 || cst) return TFMPC_ERR_ARG;           // the constant term is not carried through the elements
+    if (B == 0) return TFMPC_OK;
+    if (!x0 || !states || !costs || !actions) return TFMPC_ERR_ARG;
+    const SegmentTable tab = segment_table(T, segments);
+    if (tab.count == 1)
+        return solve<double>(B, n, m, T, md, x0, states, actions, costs, K, k, V, v, nullptr, status, nullptr, workspace,
+                             workspace_bytes, stream);
+    const size_t waves = (size_t)B * tab.count;
+    if (waves > (size_t)INT32_MAX) return TFMPC_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < time_parallel_workspace_bytes(B, n, m, T, segments)) return TFMPC_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) % sizeof(double)) return TFMPC_ERR_ARG;      // doubles are carved from it
+    TvTimeParallel tp{};
+    tp.segments = tab.count;
+    tp.len = tab.len;
+    double *w = static_cast<double *>(workspace);
+    tp.elems = w; w += waves * tv_tp_elem_doubles(n);
+    tp.Vend = w; w += waves * n * n;
+    tp.vend = w; w += waves * n;
+    tp.xstart = w; w += waves * n;
+    double *gains = w; w += (size_t)B * T * m * (n + 1);
+    int32_t *st = reinterpret_cast<int32_t *>(w);
+    tp.st_condense = st;
+    tp.st_expand = st + waves;
+    tp.st_stitch = st + 2 * waves;
+    TvLqrArgsT<double> a = make_args(B, n, m, T, md);
+    a.x0 = x0;
+    a.K = K ? K : gains;
+    a.k = k ? k : gains + (size_t)B * T * m * n;
+    a.sK = (long)T * m * n; a.sk = (long)T * m;
+    a.V = V; a.v = v;
+    a.states = states; a.actions = actions; a.costs = costs; a.status = status;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // TFMPC_TVLQR_TP_PHASES=1|2: stop after the condense / the stitch launch -- for the phase split of
+    // tools/tvlqr_time_parallel_rate.py only; no output is written, and the call says so: TFMPC_TVLQR_TP_STOPPED, not OK
+    const int phases = option_int(kOptTvlqrTpPhases, 3);
+    if ((rc = tvlqr_time_parallel_f64_condense_launch(a, tp, s)) != TFMPC_OK) return rc;
+    if (phases == 1) return TFMPC_TVLQR_TP_STOPPED;
+    if ((rc = tvlqr_time_parallel_f64_stitch_launch(a, tp, s)) != TFMPC_OK) return rc;
+    if (phases == 2) return TFMPC_TVLQR_TP_STOPPED;
+    if ((rc = tvlqr_f64_expand_launch(a, tp, s)) != TFMPC_OK) return rc;
+    if (!K) a.K = nullptr;                                   // scratch gains are nobody's output
+    if (!k) a.k = nullptr;
+    return tvlqr_time_parallel_f64_finish_launch(a, tp, s);
 }
 
 }  // extern "C"

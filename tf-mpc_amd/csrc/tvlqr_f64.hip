@@ -2,7 +2,8 @@
 // n <= 32 and m <= 32.
 //
 // The double instantiation of tvlqr_wave.h's body: products on v_mfma_f64_16x16x4_f64 (wave_ops_f64.h), the folded LDS
-// layout.  The entry points are in tvlqr_dispatch.hip.
+// layout.  Also the expand kernel of the time-parallel solve: the same body on one segment of the
+// horizon.  The entry points are in tvlqr_dispatch.hip.
 #include <hip/hip_runtime.h>
 
 #include "tvlqr_wave.h"
@@ -46,6 +47,40 @@ int launch_for(const TvLqrArgsT<double> &a, bool backward, bool forward, hipStre
     return tv_wave_launch(tvlqr_f64_kernel<MAXD, false, true>, a, smem, stream);
 }
 
+// The expand phase of the time-parallel solve: the same body on segment i of instance b, between the
+// stitch's boundary state and the value function behind the segment.
+template <int MAXD>
+__global__ __launch_bounds__(kWave) void tvlqr_expand_f64_kernel(TvLqrArgsT<double> a, TvTimeParallel tp)
+{
+    extern __shared__ double smem_f64[];
+    const size_t w = blockIdx.x;
+    const int n = a.n;
+    TvSegment<double> seg;
+    seg.b = (int)(blockIdx.x / (unsigned)tp.segments);
+    const int i = (int)blockIdx.x - seg.b * tp.segments;
+    seg.t0 = i * tp.len;
+    seg.len = a.T - seg.t0 < tp.len ? a.T - seg.t0 : tp.len;
+    seg.last = i == tp.segments - 1;
+    seg.Vend = tp.Vend + w * n * n;
+    seg.vend = tp.vend + w * n;
+    seg.xstart = tp.xstart + w * n;
+    seg.status = tp.st_expand + w;
+    tvlqr_wave_body<TvF64<MAXD>, true, true, false>(a, smem_f64, seg);
+}
+
+template <int MAXD>
+int expand_for(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream)
+{
+    const size_t smem = tv_smem_elems<true>(a.n, a.m) * sizeof(double);
+    auto kern = tvlqr_expand_f64_kernel<MAXD>;
+    if (smem > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
+    if (smem > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        return TFMPC_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.B * tp.segments), dim3(kWave), smem, stream, a, tp);
+    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+}
+
 bool wave16(int n, int m) { return n <= 16 && m <= 16; }
 
 }  // namespace
@@ -57,6 +92,11 @@ const char *tvlqr_f64_kernel_name(int n, int m) { return wave16(n, m) ? "tv_f64_
 int tvlqr_f64_launch(const TvLqrArgsT<double> &a, bool backward, bool forward, hipStream_t stream)
 {
     return wave16(a.n, a.m) ? launch_for<16>(a, backward, forward, stream) : launch_for<32>(a, backward, forward, stream);
+}
+
+int tvlqr_f64_expand_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream)
+{
+    return wave16(a.n, a.m) ? expand_for<16>(a, tp, stream) : expand_for<32>(a, tp, stream);
 }
 
 }  // namespace tfmpc

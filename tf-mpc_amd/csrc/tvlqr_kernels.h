@@ -47,6 +47,25 @@ bool tvlqr_f64_supported(int n, int m);
 const char *tvlqr_f64_kernel_name(int n, int m);
 int tvlqr_f64_launch(const TvLqrArgsT<double> &a, bool backward, bool forward, hipStream_t stream);
 
+// The time-parallel double solve (tfmpc_tvlqr_solve_time_parallel_f64): the horizon in `segments`
+// pieces of `len` steps (the last one shorter), one wave per (instance, segment), w = b * segments + i.
+struct TvTimeParallel {
+    int segments, len;
+    double *elems;                // [B segments][3 n n + 2 n]: A, G, H, b, h of the condensed segment
+    double *Vend, *vend;          // [B segments][n][n], [n]: the value function at the segment's end
+    double *xstart;               // [B segments][n]: the state at the segment's start
+    int32_t *st_condense, *st_stitch, *st_expand;     // [B segments], [B], [B segments]
+};
+__host__ __device__ constexpr size_t tv_tp_elem_doubles(int n) { return (size_t)3 * n * n + 2 * n; }
+
+const char *tvlqr_time_parallel_f64_kernel_name(int n, int m);
+// condense + stitch (tvlqr_time_parallel_f64.hip), expand (tvlqr_f64.hip: the body of tvlqr_wave.h on a segment), then
+// the status OR and the NaN fill of flagged instances (every non-NULL output of a); a.cst is NULL
+int tvlqr_time_parallel_f64_condense_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream);
+int tvlqr_time_parallel_f64_stitch_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream);
+int tvlqr_f64_expand_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream);
+int tvlqr_time_parallel_f64_finish_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream);
+
 // tfmpc_tvlqr_solve_f32 (same arguments, K = k = V = v = cst = NULL) on a MASKED model: for every set bit i of
 // mask[b][t], column n + i of F_t is read as zero, row and column n + i of C_t as zero with a unit diagonal, and
 // entry n + i of c_t as zero, so that row i of K_t and k_t[i] are exactly zero.  The mask is applied as the operands

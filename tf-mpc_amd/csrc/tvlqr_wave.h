@@ -1,5 +1,6 @@
 // tvlqr_wave.h -- the ONE body of the wave-per-instance time-varying LQR: LDS layout, backward
-// sweep, rollout and launcher, instantiated in fp32 by tvlqr_generic.hip and in double by tvlqr_f64.hip.
+// sweep, rollout and launcher, instantiated in fp32 by tvlqr_generic.hip and in double by tvlqr_f64.hip (whole horizons,
+// and single segments for the time-parallel solve's expand phase).
 //
 // Per step t of the backward sweep the wave copies F_t, f_t, C_t, c_t into its LDS slice and runs the symmetric
 // recursion of the fast kernels: W = F_t^T V, Q = C_t + W F_t and V' = Q_xx + Q_xu K on the matrix cores, q = c_t + W f_t
@@ -94,37 +95,76 @@ __device__ inline TvSmem<S> tv_carve(S *base, int n, int m)
     return s;
 }
 
+// Which part of which instance a wave works on.  TvWhole: instance blockIdx.x, the whole horizon -- every constant below
+// folds and the body is the one it was.  TvSegment (the time-parallel solve's expand phase): steps
+// t0 .. t0 + len - 1 of instance b, the value function behind the segment and the state at its start read from the
+// stitch's workspace; only the LAST segment writes states[T] and the final cost.
+struct TvWhole {
+    static constexpr bool kSegment = false;
+};
+template <class S>
+struct TvSegment {
+    static constexpr bool kSegment = true;
+    int b, t0, len;
+    bool last;
+    const S *Vend, *vend;         // [n][n], [n]: the value function at step t0 + len
+    const S *xstart;              // [n]: the state at step t0
+    int32_t *status;              // this wave's own status word
+};
+
 // MASKED (DESIGN.md 3.11, fp32 only): held controls (bit i of a.mask[b][t]) are taken out of the step's model after the
 // LDS copy.
-template <class P, bool BACKWARD, bool FORWARD, bool MASKED>
-__device__ __forceinline__ void tvlqr_wave_body(const TvLqrArgsT<typename P::T> &a, typename P::T *smem)
+template <class P, bool BACKWARD, bool FORWARD, bool MASKED, class SEG = TvWhole>
+__device__ __forceinline__ void tvlqr_wave_body(const TvLqrArgsT<typename P::T> &a, typename P::T *smem, const SEG &seg = SEG())
 {
     using S = typename P::T;
     static_assert(!MASKED || sizeof(S) == sizeof(float), "the masked sweep is fp32 only");
-    const int b = blockIdx.x;
+    static_assert(!MASKED || !SEG::kSegment, "the masked sweep runs whole horizons");
+    int b;
+    if constexpr (SEG::kSegment) b = seg.b;
+    else b = blockIdx.x;
     const int lane = lane_id();
-    const int n = a.n, m = a.m, d = n + m, T = a.T;
+    const int n = a.n, m = a.m, d = n + m, Th = a.T;         // Th: the whole horizon, the outputs' layout
+    int T = Th;                                               // the steps of this wave
+    if constexpr (SEG::kSegment) T = seg.len;
+    // step t of this wave in the horizon (written so that the whole-horizon kernels see the very expressions they had)
+    auto at = [&](int t) {
+        if constexpr (SEG::kSegment) return seg.t0 + t;
+        else return t;
+    };
+    auto last_step = [&]() {
+        if constexpr (SEG::kSegment) return Th - 1;
+        else return T - 1;
+    };
     TvSmem<S> s = tv_carve<P::kFold>(smem, n, m);
     const int ldd = s.ldd, ldn = s.ldn, lda = s.lda, ldv = s.ldv;
     auto load_model = [&](int t) {
-        load_matrix(s.F, ldd, tv_at(a.F, a.sF_b, a.sF_t, b, t), n, d);
-        load_matrix(s.C, ldd, tv_at(a.C, a.sC_b, a.sC_t, b, t), d, d);
-        const S *fg = tv_at(a.f, a.sf_b, a.sf_t, b, t), *cg = tv_at(a.c, a.sc_b, a.sc_t, b, t);
+        load_matrix(s.F, ldd, tv_at(a.F, a.sF_b, a.sF_t, b, at(t)), n, d);
+        load_matrix(s.C, ldd, tv_at(a.C, a.sC_b, a.sC_t, b, at(t)), d, d);
+        const S *fg = tv_at(a.f, a.sf_b, a.sf_t, b, at(t)), *cg = tv_at(a.c, a.sc_b, a.sc_t, b, at(t));
         for (int i = lane; i < n; i += kWave) s.f[i] = fg[i];
         for (int i = lane; i < d; i += kWave) s.c[i] = cg[i];
     };
     // the final cost's (C_fin, c_fin, leading dimension): explicit, or C_{T-1}[:n,:n], c_{T-1}[:n]
-    const S *Cf = a.Cfin ? a.Cfin + (size_t)b * a.sCfin_b : tv_at(a.C, a.sC_b, a.sC_t, b, T - 1);
-    const S *cf = a.Cfin ? a.cfin + (size_t)b * a.scfin_b : tv_at(a.c, a.sc_b, a.sc_t, b, T - 1);
+    const S *Cf = a.Cfin ? a.Cfin + (size_t)b * a.sCfin_b : tv_at(a.C, a.sC_b, a.sC_t, b, last_step());
+    const S *cf = a.Cfin ? a.cfin + (size_t)b * a.scfin_b : tv_at(a.c, a.sc_b, a.sc_t, b, last_step());
     const int ldf = a.Cfin ? n : d;
+    // where the backward sweep starts: the final cost, or the value function behind the segment
+    const S *Vb = Cf, *vb = cf;
+    int ldb = ldf;
+    if constexpr (SEG::kSegment) { Vb = seg.Vend; vb = seg.vend; ldb = n; }
 
     int status = 0;
     S *Kg = a.K + (size_t)b * a.sK;
     S *kg = a.k + (size_t)b * a.sk;
+    if constexpr (SEG::kSegment) {
+        Kg += (size_t)seg.t0 * m * n;
+        kg += (size_t)seg.t0 * m;
+    }
 
     if (BACKWARD) {
-        wave_for_2d(n, n, [&](int i, int j, int) { s.V[i * ldn + j] = Cf[i * ldf + j]; });
-        for (int i = lane; i < n; i += kWave) s.v[i] = cf[i];
+        wave_for_2d(n, n, [&](int i, int j, int) { s.V[i * ldn + j] = Vb[i * ldb + j]; });
+        for (int i = lane; i < n; i += kWave) s.v[i] = vb[i];
         S cst = S(0);
         wsync();
 
@@ -132,7 +172,7 @@ __device__ __forceinline__ void tvlqr_wave_body(const TvLqrArgsT<typename P::T> 
             load_model(t);
             wsync();
             if (MASKED) {
-                const uint32_t w = a.mask[(size_t)b * T + t];
+                const uint32_t w = a.mask[(size_t)b * Th + t];
                 auto held = [&](int zi) { return zi >= n && (w >> (zi - n) & 1u); };
                 wave_for_2d(n, m, [&](int r, int j, int) { if (w >> j & 1u) s.F[r * ldd + n + j] = S(0); });
                 wave_for_2d(d, d, [&](int r, int j, int) { if (held(r) || held(j)) s.C[r * ldd + j] = (r == j) ? S(1) : S(0); });
@@ -212,26 +252,33 @@ __device__ __forceinline__ void tvlqr_wave_body(const TvLqrArgsT<typename P::T> 
             wave_for_2d(n, n, [&](int i, int j, int idx) {
                 const S x = S(0.5) * (s.Vn[i * ldv + j] + s.Vn[j * ldv + i]);
                 s.V[i * ldn + j] = x;
-                if (a.V) a.V[((size_t)b * T + t) * n * n + idx] = x;
+                if (a.V) a.V[((size_t)b * Th + at(t)) * n * n + idx] = x;
             });
             for (int i = lane; i < n; i += kWave) {
                 const S x = s.vn[i];
                 s.v[i] = x;
-                if (a.v) a.v[((size_t)b * T + t) * n + i] = x;
+                if (a.v) a.v[((size_t)b * Th + at(t)) * n + i] = x;
             }
-            if (a.cst && lane == 0) a.cst[(size_t)b * T + t] = cst;
+            if (a.cst && lane == 0) a.cst[(size_t)b * Th + at(t)] = cst;
             wsync();
         }
         if (!P::valid(cst)) status |= TFMPC_ST_NAN;
     }
 
     if (FORWARD) {
-        S *xs = a.states + (size_t)b * (T + 1) * n;
-        S *us = a.actions + (size_t)b * T * m;
-        S *cs = a.costs + (size_t)b * (T + 1);
+        S *xs = a.states + (size_t)b * (Th + 1) * n;
+        S *us = a.actions + (size_t)b * Th * m;
+        S *cs = a.costs + (size_t)b * (Th + 1);
+        if constexpr (SEG::kSegment) {
+            xs += (size_t)seg.t0 * n;
+            us += (size_t)seg.t0 * m;
+            cs += seg.t0;
+        }
         __syncthreads();                                 // gains written above are visible
         for (int i = lane; i < n; i += kWave) {
-            const S x = a.x0[(size_t)b * n + i];
+            S x;
+            if constexpr (SEG::kSegment) x = seg.xstart[i];
+            else x = a.x0[(size_t)b * n + i];
             s.z[i] = x;
             xs[i] = x;
         }
@@ -264,22 +311,34 @@ __device__ __forceinline__ void tvlqr_wave_body(const TvLqrArgsT<typename P::T> 
             for (int i = lane; i < n; i += kWave) {
                 const S x = s.xn[i];
                 s.z[i] = x;
-                xs[(size_t)(t + 1) * n + i] = x;
+                if constexpr (SEG::kSegment) {               // (the next segment writes its own first state)
+                    if (seg.last || t + 1 < T) xs[(size_t)(t + 1) * n + i] = x;
+                } else {
+                    xs[(size_t)(t + 1) * n + i] = x;
+                }
             }
             wsync();
         }
-        S part = S(0);                                     // 1/2 x^T C_fin x + c_fin^T x
-        for (int r = lane; r < n; r += kWave) {
-            S cz = S(0);
-            for (int j = 0; j < n; ++j) cz = fma(Cf[r * ldf + j], s.z[j], cz);
-            part += s.z[r] * (S(0.5) * cz + cf[r]);
+        bool last = true;
+        if constexpr (SEG::kSegment) last = seg.last;
+        if (last) {
+            S part = S(0);                                 // 1/2 x^T C_fin x + c_fin^T x
+            for (int r = lane; r < n; r += kWave) {
+                S cz = S(0);
+                for (int j = 0; j < n; ++j) cz = fma(Cf[r * ldf + j], s.z[j], cz);
+                part += s.z[r] * (S(0.5) * cz + cf[r]);
+            }
+            const S last_cost = wave_sum(part);
+            if (lane == 0) cs[T] = last_cost;
+            if (!P::valid(last_cost)) status |= TFMPC_ST_NAN;
         }
-        const S last_cost = wave_sum(part);
-        if (lane == 0) cs[T] = last_cost;
-        if (!P::valid(last_cost)) status |= TFMPC_ST_NAN;
     }
 
-    if (a.status && lane == 0) a.status[b] = status;
+    if constexpr (SEG::kSegment) {
+        if (lane == 0) *seg.status = status;
+    } else {
+        if (a.status && lane == 0) a.status[b] = status;
+    }
 }
 
 // One launch of a wave-per-instance kernel with `smem` bytes of dynamic LDS per wave.

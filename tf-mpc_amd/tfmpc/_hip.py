@@ -15,7 +15,8 @@ _LIB_PATH = os.environ.get("TFMPC_LIB") or os.path.join(os.path.dirname(os.path.
 _lib = None
 
 ERRORS = {-1: "bad argument", -2: "shape not supported by any kernel variant",
-          -3: "kernel launch failed", -4: "workspace too small"}
+          -3: "kernel launch failed", -4: "workspace too small",
+          1: "stopped after a phase on request (TFMPC_TVLQR_TP_PHASES is set): no output was written"}
 
 ST_SINGULAR, ST_NOT_PD, ST_NAN, ST_QP_MAXITER, ST_MAX_ATTEMPTS, ST_QP_LATER_NOT_PD, ST_ENV_FLAG = 1, 2, 4, 8, 16, 32, 64
 ST_NOT_STABILISING = 128      # tfmpc_lqr_steady_state_f32: no stabilising solution found
@@ -56,6 +57,10 @@ _SIGNATURES.update({
     "tfmpc_tvlqr_backward_f64": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P]),
     "tfmpc_tvlqr_forward_f64": (_I, _TV_MODEL + [_P, _L, _P, _L, _P, _P, _P, _P, _P]),
     "tfmpc_tvlqr_solve_f64": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    # the time-parallel double solve: tfmpc_tvlqr_solve_f64's arguments with `segments` after status
+    "tfmpc_tvlqr_time_parallel_workspace_bytes_f64": (_Z, [_I, _I, _I, _I, _I]),
+    "tfmpc_tvlqr_time_parallel_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I, _I]),
+    "tfmpc_tvlqr_solve_time_parallel_f64": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "tfmpc_tvlqr_vjp_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     # states actions, g_states g_actions g_costs, dF df dC dc (+ batch, time strides), dCfin dcfin dx0 (+ batch stride)
     "tfmpc_tvlqr_vjp_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3 + [_P, _P, _Z, _P]),
@@ -105,6 +110,7 @@ ENV_LQ, ENV_NAVLQR, ENV_NAVIGATION, ENV_HVAC, ENV_RESERVOIR, ENV_USER = range(6)
 ENV_MAX_PARAMS = 10
 MAX_ALPHAS = 16
 TRACE_COLS = 11          # TFMPC_TRACE_COLS
+TVLQR_TP_STOPPED = 1     # TFMPC_TVLQR_TP_STOPPED: the time-parallel solve stopped after a phase on request, no output written
 MIN_VERSION = 320        # tfmpc_version() this binding was written against (include/tfmpc_hip.h)
 
 

@@ -14,6 +14,10 @@ Precision: the default ``dtype=torch.float32`` casts every operand to fp32, floa
 operands, ``x0`` and every output then stay in double.  Gradients of the double solve are opt-in:
 ``solve(x0, differentiable=True)`` / ``solve_tensors(x0, differentiable=True)`` (``tfmpc_tvlqr_vjp_f64``, DESIGN.md 3.15);
 the Riccati recursion's gradients (``backward(differentiable=True)``) are served in fp32 only.
+
+A few long horizons (B <= 64 or so, T in the hundreds or thousands): ``solve_time_parallel`` /
+:func:`tvlqr_solve_time_parallel` cut the horizon into segments that are worked on concurrently
+(``tfmpc_tvlqr_solve_time_parallel_f64``; double only, no gradients).
 """
 
 import numpy as np
@@ -376,6 +380,78 @@ class TimeVaryingLQR:
         out["workspace"] = workspace
         return out
 
+    # -- one long horizon on many waves (tfmpc_tvlqr_solve_time_parallel_f64) ---------------
+    def default_segments(self, batch_size=None):
+        """The ``segments`` that :meth:`solve_time_parallel` picks for ``segments=None``, fitted to
+        profiles/tvlqr_time_parallel_rate.json.  In units of one sequential step a step of a segment costs
+        2.7 (condense + expand) and a segment 2.3 (its two solves in the serial stitch), so the time is
+        ``2.7 ceil(T / P) + 2.3 P``, least at ``P = sqrt(1.2 T)``; ``P`` is capped by the condense waves the device keeps
+        resident (five per compute unit) shared among the batch, and is 1 -- the sequential kernel -- where that time is
+        not below ``T``."""
+        B = max(batch_size if batch_size is not None else (self.batch_size or 1), 1)
+        T = self.horizon
+        cus = torch.cuda.get_device_properties(self.device).multi_processor_count if self.device.type == "cuda" else 256
+        segments = min(int(round((1.2 * T) ** 0.5)), (5 * cus) // B, T)
+        if segments < 2 or 2.7 * -(-T // segments) + 2.3 * segments >= T:
+            return 1
+        return segments
+
+    def solve_time_parallel(self, x0, segments=None, want_policy=False, want_value=False):
+        """The solve with the horizon cut into ``segments`` pieces that are condensed, stitched and expanded concurrently
+        (DESIGN.md 3.19): for a few long horizons, where one wavefront per instance leaves the device idle.  A
+        :class:`Trajectory`; with ``want_policy`` / ``want_value`` a tuple ``(trajectory, K, k)``, ``(trajectory, V, v)`` or
+        ``(trajectory, K, k, V, v)`` of device tensors (no ``const``: the value function's constant term is not carried
+        across segments).  ``segments=None`` picks :meth:`default_segments`; a value above the horizon is clamped, 1 is the
+        sequential solve, bit for bit.  ``last_status`` is set as in :meth:`solve_device`.  Double precision only, no
+        gradients: use ``solve(x0, differentiable=True)`` for those."""
+        out = self._time_parallel_device(x0, segments, want_policy, want_value)
+        fields = ("states", "actions", "costs") + (("K", "k") if want_policy else ()) + (("V", "v") if want_value else ())
+        tensors = [out[name] if out["batched"] else out[name][0] for name in fields]
+        traj = trajectory.Trajectory(*tensors[:3])
+        return (traj, *tensors[3:]) if tensors[3:] else traj
+
+    def _time_parallel_device(self, x0, segments=None, want_policy=False, want_value=False):
+        """One tfmpc_tvlqr_solve_time_parallel_f64 call; a dict of batched device tensors as :meth:`solve_device`'s (no
+        ``const``).  Never synchronises."""
+        if self.dtype != torch.float64:
+            raise NotImplementedError("the time-parallel solve is served in double only: build the problem with "
+                                      "dtype=torch.float64")
+        if tvlqr_grad.wants_grad(*self._sources, x0):
+            raise NotImplementedError("the time-parallel solve has no gradients (the double VJP's adjoint solve is serial in "
+                                      "the horizon): use solve(x0, differentiable=True), or detach the operands and x0")
+        if segments is not None and int(segments) < 1:
+            raise ValueError(f"segments must be at least 1, got {segments}")
+        lib = _hip.require_gpu()
+        n, m, T = self.state_size, self.action_size, self.horizon
+        x0 = self._prep_x0(x0)
+        B = self._resolve_batch(x0)
+        Bk = B if B is not None else 1
+        if x0.dim() == 2:
+            x0 = x0.unsqueeze(0).expand(Bk, n, 1).contiguous()
+        segments = self.default_segments(Bk) if segments is None else int(segments)
+        dev, dt = self.device, self.dtype
+        states = torch.empty((Bk, T + 1, n, 1), device=dev, dtype=dt)
+        actions = torch.empty((Bk, T, m, 1), device=dev, dtype=dt)
+        costs = torch.empty((Bk, T + 1, 1, 1), device=dev, dtype=dt)
+        status = (torch.zeros if Bk == 0 else torch.empty)((Bk,), dtype=torch.int32, device=dev)
+        K = k = V = v = None
+        if want_policy:
+            K, k = torch.empty((Bk, T, m, n), device=dev, dtype=dt), torch.empty((Bk, T, m, 1), device=dev, dtype=dt)
+        if want_value:
+            V, v = torch.empty((Bk, T, n, n), device=dev, dtype=dt), torch.empty((Bk, T, n, 1), device=dev, dtype=dt)
+        ws_bytes = int(lib.tfmpc_tvlqr_time_parallel_workspace_bytes_f64(Bk, n, m, T, segments))
+        workspace = torch.empty(max(ws_bytes // 8, 1), dtype=dt, device=dev)
+        rc = lib.tfmpc_tvlqr_solve_time_parallel_f64(
+            Bk, n, m, T, *self._model_args(), _hip.ptr(x0), _hip.ptr(states), _hip.ptr(actions), _hip.ptr(costs),
+            _hip.ptr(K), _hip.ptr(k), _hip.ptr(V), _hip.ptr(v), None, _hip.ptr(status), segments,
+            _hip.ptr(workspace), workspace.numel() * 8, _hip.stream())
+        _hip.check(rc, "tfmpc_tvlqr_solve_time_parallel_f64")
+        self.last_status = status
+        out = dict(states=states, actions=actions, costs=costs, status=status, K=K, k=k, V=V, v=v)
+        out = {name: t for name, t in out.items() if t is not None}
+        out.update(batched=B is not None, segments=segments, workspace=workspace)
+        return out
+
     def solve(self, x0, differentiable=False):
         """A :class:`Trajectory`; with autograd recording and an operand or ``x0`` requiring grad, a
         :class:`~tfmpc.solvers.tvlqr_grad.TensorTrajectory` differentiable through ``tfmpc_tvlqr_vjp_f32``.  With
@@ -427,4 +503,19 @@ class TimeVaryingLQR:
         return states, actions, costs
 
 
-__all__ = ["TimeVaryingLQR"]
+def tvlqr_solve_time_parallel(F, f, C, c, x0, segments=None, C_final=None, c_final=None):
+    """The time-parallel double-precision solve of :meth:`TimeVaryingLQR.solve_time_parallel` on operands in
+    :class:`TimeVaryingLQR`'s shapes: ``(states, actions, costs)`` as float64 device tensors -- ``states[(B,)T+1,n,1]``,
+    ``actions[(B,)T,m,1]``, ``costs[(B,)T+1,1,1]``.  ``F`` must be float64 (tensor or numpy): an fp32 problem raises
+    ``NotImplementedError``, as does an operand or ``x0`` that requires grad."""
+    kind = F.dtype if isinstance(F, torch.Tensor) else np.asarray(F).dtype
+    if kind not in (torch.float64, np.float64):
+        raise NotImplementedError(f"the time-parallel solve is served in double only (dtype=torch.float64), F is {kind}")
+    device = next((t.device for t in (F, f, C, c, x0) if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
+    tv = TimeVaryingLQR(F, f, C, c, C_final, c_final, device=device, dtype=torch.float64)
+    out = tv._time_parallel_device(x0, segments)
+    states, actions, costs = out["states"], out["actions"], out["costs"]
+    return (states, actions, costs) if out["batched"] else (states[0], actions[0], costs[0])
+
+
+__all__ = ["TimeVaryingLQR", "tvlqr_solve_time_parallel"]
