@@ -32,8 +32,9 @@
 //   4. V' = Q_xx + Q_xu K: 2 x v_mfma_f32_16x16x4_f32 (the Schur-complement form of the four-term update
 //      lqr.py:97-105, equal to it in exact arithmetic).  v' = q_x + Q_xu k is 128 multiply-adds and gets no matrix tile
 //      (a 16 x 16 tile of which one column is used cost two more MFMAs, 64 cycles of the matrix pipe per step): the lanes
-//      of the elimination that hold column j of Q_ux -- and, behind it, of K -- finish v'[j] = q_x[j] + sum_a k[a] Q_ux[a][j]
-//      as ONE chain of eight FMAs, a = 0..7, the same chain in the paired and in the one-wave blocks, and store it over q_x.  Then
+//      of the elimination that hold column j of Q_ux finish it from the FORWARD elimination -- with m^_a the reduced row a and
+//      x^_a = -m^_a / d_a, v'[j] = q_x[j] + (sum_a x^_a[q_u column] m^_a[j]), which is q_x + Q_xu k written with the factors of Q_uu --
+//      as ONE chain of eight FMAs from 0, a = 0..7, and one addition, the same in the paired and in the one-wave blocks, and store it over q_x.  Then
 //      V' <- (V' + V'^T) / 2 through an LDS transpose: steps 2 and 3 use the symmetry of V, so its
 //      rounding-level antisymmetric part must not survive a step (it would grow like |F_u K|^2
 //      per step; the reference does not symmetrise, quirk Q6 of SURVEY.md).
@@ -344,18 +345,13 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                     const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds_all[pair_src]);
                     const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds_all[pair_src + 4]);
                     const float d0 = lds_all[pair_d0];
-                    // the column once more, for the value chain behind the solve (which overwrites its inputs): read twice -- volatile, or the
-                    // two reads would be merged and the second copy made with eight v_mov_b32 -- rather than read again behind the solve, where
-                    // the partner wave would wait for the round trip
-                    const f32x4 qlo = *(const volatile TFMPC_LDS f32x4 *)&lds_all[pair_src];
-                    const f32x4 qhi = *(const volatile TFMPC_LDS f32x4 *)&lds_all[pair_src + 4];
                     float vnext = lds_all[pair_qx];                 // q_x[j] in the lanes of Q_ux column j
                     P2[0] = f32x2{lo[0], lo[1]}; P2[1] = f32x2{lo[2], lo[3]};
                     P2[2] = f32x2{hi[0], hi[1]}; P2[3] = f32x2{hi[2], hi[3]};
-                    const float Qc[8] = {qlo[0], qlo[1], qlo[2], qlo[3], qhi[0], qhi[1], qhi[2], qhi[3]};
                     float Pr[8];
-                    ldlt8_pair_solve_neg(P2, Pr, d0, min_pivot_rows, Qc, vnext);
-                    lds_all[pair_qx] = vnext;                       // v'[j] = q_x[j] + sum_a k[a] Q_ux[a][j] in place of q_x[j]
+                    float corr = 0.0f;                              // sum_a x^_a[q_u] m^_a[j] = (Q_xu k)[j], summed on its own
+                    ldlt8_pair_solve_neg(P2, Pr, d0, min_pivot_rows, corr);
+                    lds_all[pair_qx] = vnext + corr;                // v'[j] in place of q_x[j]
                     // K~ of both slices: columns 0..15 = K, column 24 = k (the copies of Q_uu's lanes land in columns 16..23, which nobody reads)
                     f32x4 klo, khi;
 #pragma unroll
@@ -368,15 +364,12 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 lds_sync();
                 // rows (2k, 2k+1) share a register pair so that one v_pk_fma_f32 updates both
                 f32x2 M2[4];
-                float Qc[8];                     // the lane's column as it came in: lanes c < 16 hold Q_ux[0..7][c]
                 {
                     const int c = lane & 31;
                     const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8]);
                     const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8 + 4]);
                     M2[0] = f32x2{lo[0], lo[1]}; M2[1] = f32x2{lo[2], lo[3]};
                     M2[2] = f32x2{hi[0], hi[1]}; M2[3] = f32x2{hi[2], hi[3]};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { Qc[r] = lo[r]; Qc[4 + r] = hi[r]; }
                 }
                 float vnext = lds[kQx + (lane & 15)];        // q_x[c]
                 float qu_saved[8];
@@ -384,22 +377,28 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
 #pragma unroll
                     for (int p = 0; p < 8; ++p) qu_saved[p] = readlane(M2[p >> 1][p & 1], 24);
                 }
-                // K~ = -Q_uu^-1 [Q_ux | . | q_u]   (lqr.py:84-87; LDL^T on the upper triangle, wave_ldlt8.h)
+                // K~ = -Q_uu^-1 [Q_ux | . | q_u]   (lqr.py:84-87; LDL^T on the upper triangle), as the two halves of wave_ldlt8.h's solve
+                // (wave_ldlt8_pair.h): the elimination leaves the reduced rows m^ in M2 and x^ = -m^ / d in N2
+                f32x2 N2[4];
+                float nl[8][8];
+                ldlt8_eliminate_neg(M2, N2, nl, min_pivot_bits);
+                // v'[c] = q_x[c] + (sum_a x^_a[q_u] m^_a[c]) in place of q_x[c]: the chain of the paired solve (wave_ldlt8_pair.h), term for term
+                // from 0, and one addition to q_x[c], so that both kinds of block give the same bits
+                if constexpr (!decltype(LAST)::value) {
+                    float corr = 0.0f;
+#pragma unroll
+                    for (int p = 0; p < 8; ++p) corr = fmaf(readlane(N2[p >> 1][p & 1], 24), M2[p >> 1][p & 1], corr);
+                    vnext += corr;
+                    if (lane < N) lds[kQx + lane] = vnext;
+                }
                 float Mr[8];
-                ldlt8_solve_neg(M2, Mr, min_pivot_bits);
+                ldlt8_backsub_neg(N2, nl, Mr);
                 float kb[8];                     // k = -Q_uu^-1 q_u (column 24), wave-uniform
 #pragma unroll
                 for (int p = 0; p < 8; ++p) kb[p] = readlane(Mr[p], 24);
                 if (VALUE) {
 #pragma unroll
                     for (int p = 0; p < 8; ++p) quk = fmaf(kb[p], qu_saved[p], quk);   // k^T q_u
-                }
-                // v'[c] = q_x[c] + sum_a k[a] Q_ux[a][c] in place of q_x[c]: the chain of the paired solve (wave_ldlt8_pair.h), term for term,
-                // so that both kinds of block give the same bits
-                if constexpr (!decltype(LAST)::value) {
-#pragma unroll
-                    for (int p = 0; p < 8; ++p) vnext = fmaf(kb[p], Qc[p], vnext);
-                    if (lane < N) lds[kQx + lane] = vnext;
                 }
                 // K~: columns 0..15 = K, column 24 = k
                 if (lane < 32) {
