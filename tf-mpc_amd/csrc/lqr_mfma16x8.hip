@@ -84,9 +84,25 @@ using namespace bf3;      // bf16x3 product helpers (mfma_bf16x3.h)
 // included, which is the last time a wave of a paired block touches its PARTNER's slice -- has completed in both waves before either
 // writes a rollout row.  Backward-only and forward-only launches use one of the two layouts alone.
 //   sweep
-constexpr int kMs = 0;          // [32 cols][8 rows]  elimination input, column-major
-constexpr int kKs = 256;        // [32 cols][8 rows]  K~ = -Q_uu^-1 [Q_ux | . | q_u], column-major
-constexpr int kVt = 512;        // V' transpose staging [16 cols][kVtLd]
+// Column stride of the two column-major arrays, in floats (a multiple of 4: 16-byte accesses).  Eight rows are used.  At a stride of 8 (32 B)
+// the columns i and i + 4 start on the same one of the 32 banks that dword reads and all stores are spread over, and i and i + 8 on the same
+// of the 64 banks of the 8- and 16-byte reads: every access of the step but the transpose's stores was a two- or four-way bank conflict,
+// 58 of the 102 LDS-array cycles of an instance's step.  At 12 the 16-byte stores of the staging and both accesses of the paired solve
+// are conflict-free and the dword reads of the value update two-way: 56 cycles (tools/probes/lds_banks.py, profiles/r14_mfma16x8_budget.md).
+// -DTFMPC_LQR_COLS=8 rebuilds the earlier layout, float for float (A/B builds).
+#ifndef TFMPC_LQR_COLS
+#define TFMPC_LQR_COLS 12
+#endif
+constexpr int kCols = TFMPC_LQR_COLS;
+// Gains of a step that ran the value update go to HBM from that update's registers (see the gain stores); -DTFMPC_LQR_GAIN_REGS=0 re-reads K~ (A/B builds)
+#ifndef TFMPC_LQR_GAIN_REGS
+#define TFMPC_LQR_GAIN_REGS 1
+#endif
+constexpr bool kGainRegs = TFMPC_LQR_GAIN_REGS != 0;
+static_assert(kCols % 4 == 0 && kCols >= 8,"columns are 16-byte aligned and hold eight rows; the 32 floats of q_x and the parking row fit columns 28..31");
+constexpr int kMs = 0;                    // [32 cols][kCols]  elimination input, column-major
+constexpr int kKs = kMs + 32 * kCols;     // [32 cols][kCols]  K~ = -Q_uu^-1 [Q_ux | . | q_u], column-major
+constexpr int kVt = kKs + 32 * kCols;     // V' transpose staging [16 cols][kVtLd]
 constexpr int kVtLd = 20;
 constexpr int kSweepFloats = kVt + 16 * kVtLd;
 //   rollout
@@ -98,6 +114,7 @@ constexpr int kZld = 26;        // even (8-byte aligned rows), 26 n mod 32 disti
 constexpr int kTC = TFMPC_LQR_TC;         // timesteps per rollout chunk (T = 50 fits one chunk of 52)
 constexpr int kRolloutFloats = kZs + (kTC + 1) * kZld + 6;
 constexpr int kLdsFloats = kSweepFloats > kRolloutFloats ? kSweepFloats : kRolloutFloats;
+static_assert(kSweepFloats <= kRolloutFloats, "the sweep's layout fits under the rollout's: a wider column stride must not grow the slice (five waves per SIMD)");
 static_assert(kLdsFloats % 4 == 0, "slices are 16-byte aligned (pair_src, the 16-byte accesses of the sweep)");
 #ifndef TFMPC_LQR_RING
 #define TFMPC_LQR_RING 4
@@ -265,21 +282,26 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
         // with equal values), and the lanes of Q_ux column j turn q_x[j] into v'[j] in place (pair_qx; step 4).
         const int pj = lane & 15, prow = (lane >> 4) & 1;
         const int pcol = pj >= 8 ? pj - 8 + 8 * prow : (pj == 0 ? N + M : N + pj);
-        const int pair_src = PAIR ? 4 * pinned(((lane >> 5) * kLdsFloats + kMs + pcol * 8) / 4) : 0;       // (a multiple of 4 floats by construction: 16-byte LDS accesses)
-        const int pair_d0 = (lane >> 5) * kLdsFloats + kMs + N * 8;      // Q_uu[0][0] of the lane's system
-        constexpr int kZero = kMs + 25 * 8;      // columns 25..31 of the elimination input are never written by step 3
+        const int pair_src = PAIR ? 4 * pinned(((lane >> 5) * kLdsFloats + kMs + pcol * kCols) / 4) : 0;       // (a multiple of 4 floats by construction: 16-byte LDS accesses)
+        const int pair_d0 = (lane >> 5) * kLdsFloats + kMs + N * kCols;      // Q_uu[0][0] of the lane's system
+        constexpr int kZero = kMs + 25 * kCols;  // columns 25..31 of the elimination input are never written by step 3
         // ... and are the only part of the slice that is read before it is written: column 25 as the zero operand (t01_src below), all of
-        // them by the elimination's lanes 25..31 (whose results nobody reads; the paired elimination reads columns 0..24 only).  q_x, then v',
-        // overwrites 28, 29 every step, and in a paired launch the solver's Q_uu lanes park their (meaningless) chain results in 30, 31, which
-        // nothing reads there; every step writes the columns 0..24 of the input and every column of K~ that is read (PAIR: 0..15 and 24, else
-        // all) before it reads them, and the transpose staging likewise.  Column 25 stays zero.
-        if (lane < kKs - kZero) lds[kZero + lane] = 0.0f;
-        constexpr int kQx = kMs + 28 * 8;        // q_x staging in pad columns 28, 29; v' takes its place behind the elimination
-        constexpr int kPark = kMs + 30 * 8;      // pad columns 30, 31
+        // them by the elimination's lanes 25..31 (whose results nobody reads; the paired elimination reads columns 0..24 only).  So the
+        // whole tail of the array, from column 25 to its end at any stride, is zeroed here once.  q_x, then v', overwrites the 16 floats
+        // from column 28 on every step, and in a paired launch the solver's Q_uu lanes park their (meaningless) chain results in the 16
+        // floats behind those, which nothing reads there (at stride 8 these are the columns 28, 29 and 30, 31; at a wider stride the 32
+        // floats end inside column 30: they are addressed as one run of floats, not as columns, the tail being contiguous at any
+        // stride); every step writes the rows 0..7 of the columns 0..24 of the input and of every column of K~ that is read (PAIR: 0..15
+        // and 24, else all) before it reads them, and the transpose staging likewise; rows 8.. of a column are never read.  Column 25
+        // stays zero.
+        for (int z = kZero + lane; z < kKs; z += kWave) lds[z] = 0.0f;
+        constexpr int kQx = kMs + 28 * kCols;    // q_x staging, 16 floats (16-byte aligned: t01_src); v' takes its place behind the elimination
+        constexpr int kPark = kQx + 16;          // parking, 16 floats: with q_x one run of 32 floats, so that pair_qx covers the 32 banks once
+        static_assert(kPark + 16 <= kKs, "q_x and the parking floats lie inside the tail of the elimination input");
         const int pair_qx = (lane >> 5) * kLdsFloats + (pj >= 8 ? kQx + pj - 8 + 8 * prow : kPark + pj + 8 * prow);
         const int t01_src = (i == M) ? kQx + 4 * q : kZero;
         // loop-invariant addresses of the step (pinned: see above)
-        const int g0_src = pinned(kKs + i * 8 + q);                  // K[4s+q][i]
+        const int g0_src = pinned(kKs + i * kCols + q);              // K[4s+q][i]
         const int vt_dst = pinned(kVt + 4 * q * kVtLd + i);          // V' transpose staging, element [row 4q][column i]
         unsigned offK = 8u * lane, offk = 4u * lane;                 // byte offsets of this lane's gains inside a step (EXACT)
         __syncthreads();
@@ -332,8 +354,8 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
             }
             // 3. [Q_ux | Q_uu | q_u] -> column-per-lane layout through LDS; Q_xu and q_x staged
             if (q < 2) {
-                *reinterpret_cast<f32x4 *>(&lds[kMs + i * 8 + 4 * q]) = T01t;                    // Q_ux[4q+r][i]
-                if (i <= M) *reinterpret_cast<f32x4 *>(&lds[kMs + (N + i) * 8 + 4 * q]) = T11;
+                *reinterpret_cast<f32x4 *>(&lds[kMs + i * kCols + 4 * q]) = T01t;                // Q_ux[4q+r][i]
+                if (i <= M) *reinterpret_cast<f32x4 *>(&lds[kMs + (N + i) * kCols + 4 * q]) = T11;
             } else if (q == 2) {
                 lds[kQx + i] = T01t[0];                                                          // q_x[i]
             }
@@ -366,8 +388,8 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 f32x2 M2[4];
                 {
                     const int c = lane & 31;
-                    const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8]);
-                    const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * 8 + 4]);
+                    const f32x4 lo = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * kCols]);
+                    const f32x4 hi = *reinterpret_cast<const f32x4 *>(&lds[kMs + c * kCols + 4]);
                     M2[0] = f32x2{lo[0], lo[1]}; M2[1] = f32x2{lo[2], lo[3]};
                     M2[2] = f32x2{hi[0], hi[1]}; M2[3] = f32x2{hi[2], hi[3]};
                 }
@@ -405,8 +427,8 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                     f32x4 lo, hi;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { lo[r] = Mr[r]; hi[r] = Mr[4 + r]; }
-                    *reinterpret_cast<f32x4 *>(&lds[kKs + lane * 8]) = lo;
-                    *reinterpret_cast<f32x4 *>(&lds[kKs + lane * 8 + 4]) = hi;
+                    *reinterpret_cast<f32x4 *>(&lds[kKs + lane * kCols]) = lo;
+                    *reinterpret_cast<f32x4 *>(&lds[kKs + lane * kCols + 4]) = hi;
                 }
                 lds_sync();
             }
@@ -414,13 +436,16 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
             //    V': contraction over the 8 actions as 2 k-steps, a = 4s + q.
             //    v' was finished by the elimination's lanes (step 3) and stands where q_x stood: lanes i == 8 read their four rows of it,
             //    every other lane reads the always-zero pad column, so the next v is 0 there.
+            constexpr bool kFromRegs = kGainRegs && EXACT && !OUT16 && !decltype(LAST)::value;   // (gains to HBM, below)
+            float g0r[2] = {0.0f, 0.0f};
             if constexpr (!decltype(LAST)::value) {
                 const f32x4 vacc = *reinterpret_cast<const f32x4 *>(&lds[t01_src]);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-                    const float ax = lds[kMs + i * 8 + 4 * s2 + q];            // Q_xu[i][4s+q] = Q_ux[4s+q][i]
+                    const float ax = lds[kMs + i * kCols + 4 * s2 + q];        // Q_xu[i][4s+q] = Q_ux[4s+q][i]
                     const float g0 = lds[g0_src + 4 * s2];                     // K[4s+q][i]
                     T00 = mfma(ax, g0, T00);
+                    g0r[s2] = g0;
                 }
                 // V' <- (V' + V'^T) / 2 (transpose through LDS).  The elimination above reads only the
                 // upper triangle of Q_uu; that is consistent only while V carries no antisymmetric part
@@ -440,25 +465,35 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
                 vd = vacc;
             }
             // gains to HBM, row-major K[t][a][j], k[t][a] (the public layout)
-            if (live) {
+            // A step that ran the value update holds them already (EXACT, no 16-bit copies): lane (i, q) = 16 q + i read K[q][i] and
+            // K[4 + q][i] as the g0 operands of step 4, and row-major those are the floats `lane` and 64 + `lane` of K[t] -- two dword
+            // stores of 256 contiguous bytes per wave each, no second read of K~.  Same values, same bits.
+            if constexpr (kFromRegs) {
+                if (live) {
+                    const gbytes Kt = uniform_base(Kg + (size_t)t * (M * N));
+                    gstore(Kt, offk, g0r[0]);
+                    gstore(Kt + 4 * kWave, offk, g0r[1]);
+                    if (lane < M) gstore(uniform_base(kg + (size_t)t * M), offk, lds[kKs + 24 * kCols + lane]);
+                }
+            } else if (live) {
                 const int ka = lane >> 3, jc = lane & 7;
                 float2 kv;
-                kv.x = lds[kKs + (2 * jc) * 8 + ka];
-                kv.y = lds[kKs + (2 * jc + 1) * 8 + ka];
+                kv.x = lds[kKs + (2 * jc) * kCols + ka];
+                kv.y = lds[kKs + (2 * jc + 1) * kCols + ka];
                 if (EXACT) {
                     gstore(uniform_base(Kg + (size_t)t * (M * N)), offK, f32x2{kv.x, kv.y});
-                    if (lane < M) gstore(uniform_base(kg + (size_t)t * M), offk, lds[kKs + 24 * 8 + lane]);
+                    if (lane < M) gstore(uniform_base(kg + (size_t)t * M), offk, lds[kKs + 24 * kCols + lane]);
                 } else {
                     if (ka < m && 2 * jc < n) Kg[(size_t)t * m * n + ka * n + 2 * jc] = kv.x;
                     if (ka < m && 2 * jc + 1 < n) Kg[(size_t)t * m * n + ka * n + 2 * jc + 1] = kv.y;
-                    if (lane < m) kg[(size_t)t * m + lane] = lds[kKs + 24 * 8 + lane];
+                    if (lane < m) kg[(size_t)t * m + lane] = lds[kKs + 24 * kCols + lane];
                 }
                 if (OUT16 && a.K16) {                      // 16-bit copy of the policy (the rollout reads the fp32 gains)
                     uint16_t *Ko = a.K16 + ((size_t)b * T + t) * (m * n);
                     if (ka < m && 2 * jc < n) Ko[ka * n + 2 * jc] = lqr_to_bf16(kv.x);
                     if (ka < m && 2 * jc + 1 < n) Ko[ka * n + 2 * jc + 1] = lqr_to_bf16(kv.y);
                 }
-                if (OUT16 && a.k16 && lane < m) a.k16[((size_t)b * T + t) * m + lane] = lqr_to_bf16(lds[kKs + 24 * 8 + lane]);
+                if (OUT16 && a.k16 && lane < m) a.k16[((size_t)b * T + t) * m + lane] = lqr_to_bf16(lds[kKs + 24 * kCols + lane]);
             }
             if (VALUE) {
                 // const += 1/2 k^T Q_uu k + k^T q_u + 1/2 f^T V f + f^T v with Q_uu k = -q_u
@@ -499,7 +534,7 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave) TFMPC_LQR_OCCUPANCY void 
         if constexpr (PAIR) {
             // each wave holds the pivots of the steps it eliminated, for BOTH instances: exchanged through column 25 of K~ (never read or
             // written by the paired step), own slice [instance of wave 0, instance of wave 1]
-            constexpr int kMinPv = kKs + 25 * 8;
+            constexpr int kMinPv = kKs + 25 * kCols;
             if ((lane & 31) == 0) lds[kMinPv + (lane >> 5)] = __builtin_bit_cast(float, min_pivot_rows);
             block_lds_sync();
             const int p0 = __builtin_bit_cast(int, lds_all[kMinPv + wave]), p1 = __builtin_bit_cast(int, lds_all[kLdsFloats + kMinPv + wave]);
