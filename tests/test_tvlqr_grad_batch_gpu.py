@@ -1,6 +1,6 @@
 """The batch-summed gradients of the time-varying LQR on the MI355X past one reduction chunk: the reductions of
 tfmpc_tvlqr_vjp_f32 and tfmpc_tvlqr_box_vjp_f32 (vjp_reduce_steps_mfma16 for n <= 16, n + m <= 32, vjp_reduce_steps
-otherwise, vjp_reduce_steps_stage2, vjp_reduce_stage1 / stage2, box_reduce_bounds / box_reduce_final) against the fp64
+otherwise, vjp_reduce_steps_stage2, vjp_reduce_final, box_reduce_bounds / box_reduce_final) against the fp64
 closed form summed over the batch (tests/tvlqr_grad_batch_ref.py), at batches of 17, 256, 257 and 519 instances -- a
 second LDS tile, an exactly full chunk of 256, a one-instance last chunk, three chunks with a tail of 4 + 3 -- and at
 the shape edges of the two per-step reductions.

@@ -128,7 +128,8 @@ def test_the_vjp_kernels_use_no_scratch():
         text = open(out).read()
     found = re.findall(r"\.name:\s+(\S*(?:vjp_|batch_sum_)\S*)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
                        r"\s+\.vgpr_spill_count:\s+(\d+)", text)
-    assert len(found) == 7, found
+    # vjp_fold_kernel, vjp_sweep_kernel, vjp_reduce_final, vjp_reduce_steps, vjp_reduce_steps_mfma16, vjp_reduce_steps_stage2
+    assert len(found) == 6, found
     for name, private, vgprs, spills in found:
         assert int(private) == 0 and int(spills) == 0 and int(vgprs) <= 256, (name, private, vgprs, spills)
 

@@ -143,6 +143,17 @@ def test_batch_sums_across_chunk_edges(B):
         _check(got, refs, f"chunks (4, 2, 3) B={B} {'+'.join(shared)}", shared)
 
 
+@pytest.mark.parametrize("n,m,T,shared,final", [(17, 2, 2, MODEL, False), (17, 2, 2, ("Cfin", "cfin", "x0"), True),
+                                                (4, 2, 3, ("Cfin", "cfin", "x0"), True)])
+def test_scalar_and_final_sums_across_chunk_edges(n, m, T, shared, final):
+    """B = 257 is sixteen full LDS tiles plus a second chunk of one instance.  n = 17 is the smallest shape off the
+    matrix-core sum: the scalar per-step sums, with the default final cost's second pass at t = T - 1 (T = 2 has a step with
+    and a step without it); the shared final cost and x0 are the one-record-per-instance sums."""
+    user, w, refs = _case(n, m, T, 257, shared=shared, final=final, seed=257)
+    got, _ = _grads(user, w)
+    _check(got, refs, f"chunk edges ({n}, {m}, {T}) B=257 {'+'.join(shared)}", shared)
+
+
 # ---- what the value-function costates buy -----------------------------------------------------------------------------
 
 @pytest.mark.parametrize("seed", [0, 1])

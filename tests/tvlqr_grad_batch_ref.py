@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY -- fp64 oracles of the BATCH-SUMMED gradients of the time-varying LQR (operands without a
-batch axis: ``vjp_reduce_*`` and ``box_reduce_*`` of tf-mpc_amd/csrc/tvlqr_vjp.hip) at batches of more than one
+batch axis: ``vjp_reduce_*`` of tf-mpc_amd/csrc/tvlqr_vjp_common.h and ``box_reduce_*`` of tvlqr_vjp.hip) at batches of more than one
 reduction chunk, built on tests/tvlqr_grad_ref.py.  Shared by tests/test_tvlqr_grad_batch_cpu.py, which shows that the
 references are inside every budget and bound, and tests/test_tvlqr_grad_batch_gpu.py, which holds the kernels to them.
 
@@ -20,7 +20,7 @@ import tvlqr_grad_ref as gref
 import tvlqr_ref
 from test_tvlqr_grad_gpu import MODEL, _case, _oracles, _reduce
 
-CHUNK = 256                       # kChunk of tvlqr_vjp.hip: instances per stage-1 partial sum
+CHUNK = 256                       # kChunk of tvlqr_vjp_common.h: instances per stage-1 partial sum
 U32 = 2.0 ** -24                  # fp32 unit roundoff
 
 # how the operands are shared: the keywords of test_tvlqr_grad_gpu._case
@@ -30,7 +30,7 @@ SHARING = dict(batch=dict(shared=MODEL),                                 # one g
                F=dict(shared=("F",)),                                    # wantC false, factor records stored
                Cc=dict(shared=("C", "c")),                               # wantF false, no factor store
                f1=dict(shared=("f",), const=("f",)),
-               final=dict(final="shared", x0_shared=True),               # vjp_reduce_stage1 / stage2
+               final=dict(final="shared", x0_shared=True),               # vjp_reduce_final / steps_stage2
                Ffc=dict(shared=("F", "f", "c")))                         # C per instance: one instance's C can be spoilt
 
 EDGE_SHAPES = [(16, 8), (20, 10)]                  # one shape per reduction kernel (matrix cores; LDS tiles)

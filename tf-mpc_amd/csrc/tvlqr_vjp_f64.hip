@@ -20,9 +20,8 @@
 //                           (dlam_{t+1}, lam_{t+1}) per (b, t).  It reads V, never F_t or C_t.  <LOOP = true>: one wavefront
 //                           per instance walks t = T - 1 .. 0 for the per-instance outputs whose TIME stride is 0, so that
 //                           one lane owns an element and adds its terms in time order (no atomics).
-//   4. vjp_reduce_*         gradients with batch stride 0, as tvlqr_vjp.hip: one pass per (chunk of instances, step) --
-//                           GEMMs over instances on v_mfma_f64_16x16x4_f64 for n <= 16, d <= 32, LDS-tiled scalar sums
-//                           otherwise -- then the chunks (and steps) in a fixed order.
+//   4. vjp_reduce_*         gradients with batch stride 0, summed over the batch in a fixed order: the kernels and the code
+//                           that enqueues them are tvlqr_vjp_common.h's, shared with tvlqr_vjp.hip (as is the fold's body).
 // An instance whose adjoint solve sets a status bit contributes NaN (its own rows, and every batch sum that includes it).
 // The build is -ffp-contract=off: every fused multiply-add is a written fma().  No scratch memory.
 #include <hip/hip_runtime.h>
@@ -31,95 +30,23 @@
 #include <cstdint>
 
 #include "tvlqr_kernels.h"
+#include "tvlqr_vjp_common.h"
 
 using namespace tfmpc;
 
 namespace {
 
-constexpr int kChunk = 256;          // instances per stage-1 partial sum
-constexpr int kTile = 16;            // records per LDS tile in stage 1
-constexpr int kRedThreads = 256;
-constexpr int kEpt = 4;              // output elements per thread per pass in stage 1
-constexpr int kWaveThreads = 64;     // one wavefront per (b, t) or per instance
+using Out = OutT<double>;
 
-enum Kind { kF = 0, kf, kC, kc, kCfin, kcfin, kx0, kKinds };
-
-struct Out {
-    double *p;
-    long sb, st;
+struct VjpArgs : VjpBase<double> {
+    const double *v;                 // the forward solve's v[B][T][n]
+    const double *V, *vt;            // the adjoint solve's V[B][T][n][n], v~[B][T][n] (v~_0: the base's a0)
 };
 
-struct VjpArgs {
-    int B, n, m, T;
-    const double *C, *c;             // the fold's operands (the costate kernel reads neither)
-    long sC_b, sC_t, sc_b, sc_t;
-    const double *Cf, *cf;           // V_T, v_T: the final cost (explicit, or the default's copy and c_{T-1}[:n]); row stride n
-    long sCf_b, scf_b;
-    bool dflt;                       // default final cost: its gradients go into dC_{T-1}[:n,:n], dc_{T-1}[:n]
-    const double *states, *actions, *v, *gx, *gu, *gc;
-    const double *dS, *dA, *ct, *cT; // adjoint trajectory, c~, c~_fin = v~_T
-    const double *V, *vt;            // the adjoint solve's V[B][T][n][n], v~[B][T][n]
-    const int32_t *status;
-    double *P;                       // per (b, t): (dlam_{t+1}, lam_{t+1}) [2n]
-    Out o[kKinds];
-};
-
-__device__ inline double poison_of(const int32_t *status, int b)
-{
-    return status[b] ? __builtin_nan("") : 0.0;
-}
-
-// ---- 1. fold -------------------------------------------------------------------------------------------------------
-// One wavefront per (b, t); t == T is the final step (rows < n).  With a cost gradient, C_t is staged in LDS by
-// coalesced loads (row stride d + 1) and each lane takes rows of C_t z_t + c_t.
+// ---- 1. fold (fold_body, tvlqr_vjp_common.h) -------------------------------------------------------------------------
 __global__ void __launch_bounds__(kWaveThreads) vjp_fold_kernel(VjpArgs a, double *ct, double *cT, double *Cfe, double *zer)
 {
-    extern __shared__ double sm[];
-    const int n = a.n, m = a.m, T = a.T, d = n + m, L = threadIdx.x;
-    const int b = (int)(blockIdx.x / (T + 1)), t = (int)(blockIdx.x % (T + 1));
-    const double *x = a.states + ((size_t)b * (T + 1) + t) * n;
-    if (t < T) {
-        double *sC = sm, *sz = sm + (size_t)d * (d + 1);
-        if (a.gc) {
-            const double *Ct = tv_at(a.C, a.sC_b, a.sC_t, b, t);
-            for (int e = L; e < d * d; e += kWaveThreads) sC[(e / d) * (d + 1) + e % d] = Ct[e];
-            const double *u = a.actions + ((size_t)b * T + t) * m;
-            for (int i = L; i < d; i += kWaveThreads) sz[i] = i < n ? x[i] : u[i - n];
-            __syncthreads();
-        }
-        for (int i = L; i < d; i += kWaveThreads) {
-            double g = 0.0;
-            if (i < n) { if (a.gx) g = a.gx[((size_t)b * (T + 1) + t) * n + i]; }
-            else if (a.gu) g = a.gu[((size_t)b * T + t) * m + (i - n)];
-            if (a.gc) {
-                const double w = a.gc[(size_t)b * (T + 1) + t];
-                const double *Ci = sC + (size_t)i * (d + 1);
-                double r = tv_at(a.c, a.sc_b, a.sc_t, b, t)[i];
-                for (int j = 0; j < d; ++j) r = fma(Ci[j], sz[j], r);
-                g = fma(w, r, g);
-            }
-            ct[((size_t)b * T + t) * d + i] = g;
-        }
-        return;
-    }
-    for (int i = L; i < n; i += kWaveThreads) {
-        zer[(size_t)b * n + i] = 0.0;
-        const double *Crow;
-        if (a.dflt) {                // C_{T-1}[i, :n]: copy the row into the adjoint's explicit final cost
-            Crow = tv_at(a.C, a.sC_b, a.sC_t, b, T - 1) + (size_t)i * d;
-            if (a.sCf_b != 0 || b == 0)
-                for (int j = 0; j < n; ++j) Cfe[(size_t)b * a.sCf_b + (size_t)i * n + j] = Crow[j];
-        } else {
-            Crow = a.Cf + (size_t)b * a.sCf_b + (size_t)i * n;
-        }
-        double g = a.gx ? a.gx[((size_t)b * (T + 1) + T) * n + i] : 0.0;
-        if (a.gc) {
-            double r = a.cf[(size_t)b * a.scf_b + i];
-            for (int j = 0; j < n; ++j) r = fma(Crow[j], x[j], r);
-            g = fma(a.gc[(size_t)b * (T + 1) + T], r, g);
-        }
-        cT[(size_t)b * n + i] = g;
-    }
+    fold_body<double, false>(a, ct, cT, Cfe, zer, nullptr);
 }
 
 // ---- 3. value-function costates and per-instance gradients -----------------------------------------------------------
@@ -144,7 +71,7 @@ __global__ void __launch_bounds__(kWaveThreads) vjp_costate_kernel(VjpArgs a, un
     const int n = a.n, m = a.m, T = a.T, d = n + m, L = threadIdx.x;
     const int b = LOOP ? (int)blockIdx.x : (int)(blockIdx.x / T);
     double *sV = sm, *x1 = sV + (size_t)n * (n + 1), *dx1 = x1 + n, *lam = dx1 + n, *dlam = lam + n, *z = dlam + n, *dz = z + d;
-    const double poison = poison_of(a.status, b);
+    const double poison = poison_of<double>(a.status, ~0, b);
     const Out &oF = a.o[kF], &of = a.o[kf], &oC = a.o[kC], &oc = a.o[kc];
     for (int t = LOOP ? T - 1 : (int)(blockIdx.x % T); t >= 0; --t) {
         const bool last = t == T - 1, first = last || !LOOP;
@@ -215,262 +142,22 @@ __global__ void __launch_bounds__(kWaveThreads) vjp_costate_kernel(VjpArgs a, un
     }
 }
 
-// ---- 4. batch reductions ---------------------------------------------------------------------------------------------
-// A record of instance b: a[n] l[n] z[d] dz[d] gc.  Step records (t < T) take a = dlam_{t+1}, l = lam_{t+1}; the final
-// record takes z[:n] = x_T, dz[:n] = dx_T, gc = gcost_T and a = dlam_0 = v~_0.
-__device__ inline void load_record(const VjpArgs &a, double *rec, int b, int t, bool fin, int lane, int nthr)
-{
-    const int n = a.n, m = a.m, T = a.T, d = n + m, W = 2 * n + 2 * d + 1;
-    const double poison = poison_of(a.status, b);
-    for (int q = lane; q < W; q += nthr) {
-        double v;
-        if (q < 2 * n) {
-            if (fin) v = q < n ? a.vt[(size_t)b * T * n + q] : 0.0;
-            else v = a.P ? a.P[((size_t)b * T + t) * 2 * n + q] : 0.0;
-        } else if (q < 2 * n + d) {
-            const int i = q - 2 * n;
-            if (fin) v = i < n ? a.states[((size_t)b * (T + 1) + T) * n + i] : 0.0;
-            else v = i < n ? a.states[((size_t)b * (T + 1) + t) * n + i] : a.actions[((size_t)b * T + t) * m + i - n];
-        } else if (q < 2 * n + 2 * d) {
-            const int i = q - 2 * n - d;
-            if (fin) v = i < n ? a.dS[((size_t)b * (T + 1) + T) * n + i] : 0.0;
-            else v = i < n ? a.dS[((size_t)b * (T + 1) + t) * n + i] : a.dA[((size_t)b * T + t) * m + i - n];
-        } else {
-            v = a.gc ? a.gc[(size_t)b * (T + 1) + (fin ? T : t)] : 0.0;
-        }
-        rec[q] = v + poison;
-    }
-}
-
-__device__ inline double contrib(int kind, const double *r, int n, int d, int e, bool fin_into_step)
-{
-    const double *al = r, *l = r + n, *z = r + 2 * n, *dz = z + d, gc = z[2 * d];
-    switch (kind) {
-    case kF: { const int i = e / d, j = e % d; return fma(al[i], z[j], l[i] * dz[j]); }
-    case kf: return al[e];
-    case kC: {
-        const int i = e / d, j = e % d;
-        if (fin_into_step && (i >= n || j >= n)) return 0.0;
-        return 0.5 * (dz[i] * z[j] + z[i] * dz[j] + gc * z[i] * z[j]);
-    }
-    case kc: if (fin_into_step && e >= n) return 0.0; return dz[e] + gc * z[e];
-    case kCfin: { const int i = e / n, j = e % n; return 0.5 * (dz[i] * z[j] + z[i] * dz[j] + gc * z[i] * z[j]); }
-    case kcfin: return dz[e] + gc * z[e];
-    default: return al[e];       // kx0
-    }
-}
-
-// dCfin, dcfin, dx0 shared by the batch: the final records of a chunk of instances.  grid (chunks); partial[chunk * nE + e]
-__global__ void __launch_bounds__(kRedThreads) vjp_reduce_final(VjpArgs a, int kind, int nE, double *partial)
-{
-    extern __shared__ double tile[];
-    const int n = a.n, d = n + a.m, W = 2 * n + 2 * d + 1;
-    const int chunk = blockIdx.x, tid = threadIdx.x;
-    const int b0 = chunk * kChunk, b1 = min(a.B, b0 + kChunk);
-    for (int e0 = 0; e0 < nE; e0 += kRedThreads * kEpt) {
-        double acc[kEpt];
-        for (int q = 0; q < kEpt; ++q) acc[q] = 0.0;
-        for (int bb = b0; bb < b1; bb += kTile) {
-            const int nb = min(kTile, b1 - bb);
-            __syncthreads();
-            for (int r = tid / 16; r < nb; r += kRedThreads / 16) load_record(a, tile + r * W, bb + r, 0, true, tid % 16, 16);
-            __syncthreads();
-            for (int r = 0; r < nb; ++r)
-                for (int q = 0; q < kEpt; ++q) {
-                    const int e = e0 + q * kRedThreads + tid;
-                    if (e < nE) acc[q] += contrib(kind, tile + r * W, n, d, e, false);
-                }
-        }
-        for (int q = 0; q < kEpt; ++q) {
-            const int e = e0 + q * kRedThreads + tid;
-            if (e < nE) partial[(size_t)chunk * nE + e] = acc[q];
-        }
-    }
-}
-
-// Fused per-step reductions: ONE pass over the records emits every requested batch-shared per-step gradient (dF, df,
-// dC, dc) of a chunk of instances at step t.  partial[(chunk * T + t) * E + off_k + e], E = n d + n + d d + d.
-__host__ __device__ inline int steps_E(int n, int d) { return n * d + n + d * d + d; }
-__host__ __device__ inline int steps_off(int k, int n, int d)
-{
-    return k == kF ? 0 : k == kf ? n * d : k == kC ? n * d + n : n * d + n + d * d;
-}
-
-// Shape-generic form: records staged in LDS tiles, scalar sums over the concatenated outputs.
-__global__ void __launch_bounds__(kRedThreads) vjp_reduce_steps(VjpArgs a, unsigned need, double *partial)
-{
-    extern __shared__ double tile[];
-    const int n = a.n, d = n + a.m, T = a.T, W = 2 * n + 2 * d + 1, E = steps_E(n, d);
-    const int chunk = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
-    const int b0 = chunk * kChunk, b1 = min(a.B, b0 + kChunk);
-    const int passes = (a.dflt && t == T - 1) ? 2 : 1;      // pass 1: the default final cost's records into dC, dc
-    for (int e0 = 0; e0 < E; e0 += kRedThreads * kEpt) {
-        double acc[kEpt];
-        int kind[kEpt], ee[kEpt];
-        for (int q = 0; q < kEpt; ++q) {
-            acc[q] = 0.0;
-            const int e = e0 + q * kRedThreads + tid;
-            kind[q] = e < steps_off(kf, n, d) ? kF : e < steps_off(kC, n, d) ? kf : e < steps_off(kc, n, d) ? kC : kc;
-            ee[q] = e - steps_off(kind[q], n, d);
-        }
-        for (int pass = 0; pass < passes; ++pass) {
-            const bool fin = pass == 1;
-            for (int bb = b0; bb < b1; bb += kTile) {
-                const int nb = min(kTile, b1 - bb);
-                __syncthreads();
-                for (int r = tid / 16; r < nb; r += kRedThreads / 16)
-                    load_record(a, tile + r * W, bb + r, t, fin, tid % 16, 16);
-                __syncthreads();
-                for (int r = 0; r < nb; ++r)
-                    for (int q = 0; q < kEpt; ++q) {
-                        const int e = e0 + q * kRedThreads + tid;
-                        if (e >= E || !(need >> kind[q] & 1u) || (fin && kind[q] <= kf)) continue;
-                        acc[q] += contrib(kind[q], tile + r * W, n, d, ee[q], fin);
-                    }
-            }
-        }
-        for (int q = 0; q < kEpt; ++q) {
-            const int e = e0 + q * kRedThreads + tid;
-            if (e < E) partial[((size_t)chunk * T + t) * E + e] = acc[q];
-        }
-    }
-}
-
-// n <= 16, d <= 32: the batch sums are GEMMs over instances on v_mfma_f64_16x16x4_f64, four instances per k-step, one
-// wave per (chunk, t).  Lane (li = lane & 15, lq = lane >> 4) loads instance b0 + lq's entries li and 16 + li straight
-// into the A / B operand slots (the f32 16x16x4 instruction's):
-//   dF = [dlam | lam] [z | dz]^T            (two 16 x 16 column tiles)
-//   dC = ([dz | z] [z | dz + gc z]^T) / 2   (2 x 2 tiles)
-// The C/D map is the f64 instruction's own: register r of lane l is row lq + 4 r, column li (wave_ops_f64.h).  df and dc
-// are per-lane sums, combined over the four k-groups in a fixed order.
-__global__ void __launch_bounds__(kWaveThreads) vjp_reduce_steps_mfma16(VjpArgs a, unsigned need, double *partial)
-{
-    using f64x4 = __attribute__((ext_vector_type(4))) double;
-    const int n = a.n, m = a.m, T = a.T, d = n + m, E = steps_E(n, d);
-    const int chunk = blockIdx.x, t = blockIdx.y, lane = threadIdx.x, li = lane & 15, lq = lane >> 4;
-    const int b0 = chunk * kChunk, b1 = min(a.B, b0 + kChunk);
-    const bool wantF = need & ((1u << kF) | (1u << kf)), wantC = need & ((1u << kC) | (1u << kc));
-    f64x4 F0 = {0, 0, 0, 0}, F1 = F0, C00 = F0, C01 = F0, C10 = F0, C11 = F0;
-    double sf = 0.0, sc0 = 0.0, sc1 = 0.0;
-    const int passes = (a.dflt && t == T - 1) ? 2 : 1;
-    for (int pass = 0; pass < passes; ++pass) {
-        const bool fin = pass == 1;
-        const int ts = fin ? T : t;
-        for (int bb = b0; bb < b1; bb += 4) {
-            const int b = bb + lq;
-            double av = 0.0, lv = 0.0, z0 = 0.0, z1 = 0.0, dz0 = 0.0, dz1 = 0.0, gc = 0.0;
-            if (b < b1) {
-                const double p = poison_of(a.status, b);
-                const double *x = a.states + ((size_t)b * (T + 1) + ts) * n, *dx = a.dS + ((size_t)b * (T + 1) + ts) * n;
-                const double *u = a.actions + ((size_t)b * T + t) * m, *du = a.dA + ((size_t)b * T + t) * m;
-                const int j1 = 16 + li;
-                if (fin) {
-                    if (li < n) { z0 = x[li]; dz0 = dx[li]; }
-                } else {
-                    if (wantF && li < n) {
-                        const double *P = a.P + ((size_t)b * T + t) * 2 * n;
-                        av = P[li] + p;
-                        lv = P[n + li] + p;
-                    }
-                    if (li < d) { z0 = li < n ? x[li] : u[li - n]; dz0 = li < n ? dx[li] : du[li - n]; }
-                    if (j1 < d) { z1 = j1 < n ? x[j1] : u[j1 - n]; dz1 = j1 < n ? dx[j1] : du[j1 - n]; }
-                }
-                z0 += p; z1 += p; dz0 += p; dz1 += p;
-                if (a.gc) gc = a.gc[(size_t)b * (T + 1) + ts];
-                gc += p;
-            }
-            const double w0 = fma(gc, z0, dz0), w1 = fma(gc, z1, dz1);
-            if (wantF && !fin) {
-                F0 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, z0, F0, 0, 0, 0);
-                F0 = __builtin_amdgcn_mfma_f64_16x16x4f64(lv, dz0, F0, 0, 0, 0);
-                F1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, z1, F1, 0, 0, 0);
-                F1 = __builtin_amdgcn_mfma_f64_16x16x4f64(lv, dz1, F1, 0, 0, 0);
-                sf += av;
-            }
-            if (wantC) {
-                C00 = __builtin_amdgcn_mfma_f64_16x16x4f64(dz0, z0, C00, 0, 0, 0);
-                C00 = __builtin_amdgcn_mfma_f64_16x16x4f64(z0, w0, C00, 0, 0, 0);
-                C01 = __builtin_amdgcn_mfma_f64_16x16x4f64(dz0, z1, C01, 0, 0, 0);
-                C01 = __builtin_amdgcn_mfma_f64_16x16x4f64(z0, w1, C01, 0, 0, 0);
-                C10 = __builtin_amdgcn_mfma_f64_16x16x4f64(dz1, z0, C10, 0, 0, 0);
-                C10 = __builtin_amdgcn_mfma_f64_16x16x4f64(z1, w0, C10, 0, 0, 0);
-                C11 = __builtin_amdgcn_mfma_f64_16x16x4f64(dz1, z1, C11, 0, 0, 0);
-                C11 = __builtin_amdgcn_mfma_f64_16x16x4f64(z1, w1, C11, 0, 0, 0);
-                sc0 += w0;
-                sc1 += w1;
-            }
-        }
-    }
-    double *out = partial + ((size_t)chunk * T + t) * E;
-    // the four k-groups of lane li, summed in a fixed order
-    auto fold4 = [&](double v) {
-        return ((__shfl(v, li) + __shfl(v, li + 16)) + __shfl(v, li + 32)) + __shfl(v, li + 48);
-    };
-    const double tf = fold4(sf), tc0 = fold4(sc0), tc1 = fold4(sc1);
-    for (int r = 0; r < 4; ++r) {
-        const int i = lq + 4 * r;
-        if (i < n) {
-            if (li < d) out[i * d + li] = F0[r];
-            if (16 + li < d) out[i * d + 16 + li] = F1[r];
-        }
-        const int cb = steps_off(kC, n, d);
-        if (i < d && li < d) out[cb + i * d + li] = 0.5 * C00[r];
-        if (i < d && 16 + li < d) out[cb + i * d + 16 + li] = 0.5 * C01[r];
-        if (16 + i < d && li < d) out[cb + (16 + i) * d + li] = 0.5 * C10[r];
-        if (16 + i < d && 16 + li < d) out[cb + (16 + i) * d + 16 + li] = 0.5 * C11[r];
-    }
-    if (lq == 0) {
-        if (li < n) out[steps_off(kf, n, d) + li] = tf;
-        if (li < d) out[steps_off(kc, n, d) + li] = tc0;
-        if (16 + li < d) out[steps_off(kc, n, d) + 16 + li] = tc1;
-    }
-}
-
-// Stage 2: out[slot * st + e] = sum over chunks, then over the slot's steps, in that order.  The one-record-per-instance
-// sums use it with T = 1, E = nE, off = 0: the chunks in order, as batch_sum.h's in-order stage 2 (which is fp32).
-__global__ void vjp_reduce_steps_stage2(const double *partial, int chunks, int T, int E, int off, int nE, bool timed,
-                                        double *out, long st)
-{
-    const int slots = timed ? T : 1;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)slots * nE) return;
-    const int slot = (int)(idx / nE), e = (int)(idx % nE);
-    const int t0 = timed ? slot : 0, t1 = timed ? slot + 1 : T;
-    double s = 0.0;
-    for (int k = 0; k < chunks; ++k)
-        for (int t = t0; t < t1; ++t) s += partial[((size_t)k * T + t) * E + off + e];
-    out[(size_t)slot * st + e] = s;
-}
-
-// ---- launch helpers --------------------------------------------------------------------------------------------------
-size_t fold_smem_bytes(int n, int m) { const size_t d = n + m; return (d * (d + 1) + d) * sizeof(double); }
-
-// ---- workspace -------------------------------------------------------------------------------------------------------
-struct Layout {
-    size_t ct, cT, Cfe, zer, dS, dA, dcost, solve, V, vt, P, partial, total;   // offsets in doubles
+// ---- workspace (tvlqr_vjp_common.h) ----------------------------------------------------------------------------------
+struct Layout : VjpPrefix {
+    size_t solve, V, vt, P, partial, total;  // offsets in doubles
     size_t solve_bytes;
 };
 
-size_t up64(size_t x) { return (x + 63) / 64 * 64; }
-
 Layout layout(int B, int n, int m, int T)
 {
-    const size_t d = n + m, Bs = B, Ts = T, chunks = (Bs + kChunk - 1) / kChunk;
     Layout L{};
-    size_t o = 0;
-    L.ct = o; o += up64(Bs * Ts * d);
-    L.cT = o; o += up64(Bs * n);
-    L.Cfe = o; o += up64(Bs * n * n);
-    L.zer = o; o += up64(Bs * n);
-    L.dS = o; o += up64(Bs * (Ts + 1) * n);
-    L.dA = o; o += up64(Bs * Ts * m);
-    L.dcost = o; o += up64(Bs * (Ts + 1));
+    size_t o = vjp_prefix(L, B, n, m, T);
     L.solve_bytes = tfmpc_tvlqr_workspace_bytes_f64(B, n, m, T);
     L.solve = o; o += up64(L.solve_bytes / sizeof(double));
-    L.V = o; o += up64(Bs * Ts * n * n);
-    L.vt = o; o += up64(Bs * Ts * n);
-    L.P = o; o += up64(Bs * Ts * 2 * n);
-    L.partial = o; o += up64(chunks * Ts * (size_t)steps_E(n, (int)d));   // >= chunks * n * n of the final-cost sums
+    L.V = o; o += up64((size_t)B * T * n * n);
+    L.vt = o; o += up64((size_t)B * T * n);
+    L.P = o; o += up64((size_t)B * T * 2 * n);
+    L.partial = o; o += vjp_partial_elems(B, n, m, T);
     L.total = o;
     return L;
 }
@@ -519,8 +206,9 @@ int tfmpc_tvlqr_vjp_f64(int B, int n, int m, int T, const double *F, long sF_b, 
     a.states = states; a.actions = actions; a.v = v; a.gx = g_states; a.gu = g_actions; a.gc = g_costs;
     a.dS = w + L.dS; a.dA = w + L.dA; a.ct = w + L.ct; a.cT = w + L.cT;
     a.V = w + L.V; a.vt = w + L.vt;
-    a.status = status;
+    a.status = status; a.poison_mask = ~0;
     a.P = w + L.P;
+    a.a0 = w + L.vt; a.sa0_b = (long)T * n;
     if (a.dflt) {                    // V_T: the fold's copy of C_{T-1}[:n,:n]; v_T = c_{T-1}[:n], contiguous in c
         a.Cf = w + L.Cfe; a.sCf_b = sC_b ? (long)n * n : 0;
         a.cf = c + (size_t)(T - 1) * sc_t; a.scf_b = sc_b;
@@ -533,8 +221,8 @@ int tfmpc_tvlqr_vjp_f64(int B, int n, int m, int T, const double *F, long sF_b, 
     for (int k = 0; k < kKinds; ++k) a.o[k] = outs[k];
 
     // 1. fold
-    hipLaunchKernelGGL(vjp_fold_kernel, dim3((unsigned)((size_t)B * (T + 1))), dim3(kWaveThreads), fold_smem_bytes(n, m), s, a,
-                       w + L.ct, w + L.cT, w + L.Cfe, w + L.zer);
+    hipLaunchKernelGGL(vjp_fold_kernel, dim3((unsigned)((size_t)B * (T + 1))), dim3(kWaveThreads),
+                       fold_smem_elems(n, m) * sizeof(double), s, a, w + L.ct, w + L.cT, w + L.Cfe, w + L.zer);
     if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
     // 2. adjoint solve: c~ per (b, t), f~ = 0 (shared), explicit final cost, x~0 = 0; V and v~ are kept
     {
@@ -563,40 +251,7 @@ int tfmpc_tvlqr_vjp_f64(int B, int n, int m, int T, const double *F, long sF_b, 
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
     }
     // 4. shared gradients
-    const int chunks = (B + kChunk - 1) / kChunk;
-    const int W = 2 * n + 2 * d + 1;
-    const int nEs[kKinds] = {n * d, n, d * d, d, n * n, n, n};
-    double *partial = w + L.partial;
-    unsigned need = 0;
-    for (int k = kF; k <= kc; ++k)
-        if (a.o[k].p && !a.o[k].sb) need |= 1u << k;
-    if (need) {                      // dF, df, dC, dc: one pass over the records, then one short sum per output
-        if (n <= 16 && d <= 32)
-            hipLaunchKernelGGL(vjp_reduce_steps_mfma16, dim3(chunks, T), dim3(kWaveThreads), 0, s, a, need, partial);
-        else
-            hipLaunchKernelGGL(vjp_reduce_steps, dim3(chunks, T), dim3(kRedThreads), (size_t)kTile * W * sizeof(double), s, a,
-                               need, partial);
-        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-        for (int k = kF; k <= kc; ++k) {
-            if (!(need >> k & 1u)) continue;
-            const bool timed = a.o[k].st != 0;
-            const size_t total = (size_t)(timed ? T : 1) * nEs[k];
-            hipLaunchKernelGGL(vjp_reduce_steps_stage2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, partial,
-                               chunks, T, steps_E(n, d), steps_off(k, n, d), nEs[k], timed, a.o[k].p, a.o[k].st);
-            if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-        }
-    }
-    for (int k = kCfin; k < kKinds; ++k) {      // final-cost and x0 sums: one record per instance, the chunks in order
-        const Out &o = a.o[k];
-        if (!o.p || o.sb) continue;
-        hipLaunchKernelGGL(vjp_reduce_final, dim3(chunks), dim3(kRedThreads), (size_t)kTile * W * sizeof(double), s, a, k,
-                           nEs[k], partial);
-        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-        hipLaunchKernelGGL(vjp_reduce_steps_stage2, dim3((unsigned)((nEs[k] + 255) / 256)), dim3(256), 0, s, partial, chunks,
-                           1, nEs[k], 0, nEs[k], false, o.p, 0L);
-        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-    }
-    return TFMPC_OK;
+    return vjp_shared_sums<double>(a, w + L.partial, s);
 }
 
 }  // extern "C"
