@@ -173,9 +173,10 @@ def test_the_steady_state_kernels_use_no_scratch():
         text = open(out).read()
     found = re.findall(r"\.name:\s+(\S*lqr_steady_state_kernel\S*)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
                        r"\s+\.vgpr_spill_count:\s+(\d+)", text)
-    assert len(found) == 2, found
+    assert len(found) == 2 == len(re.findall(r"^\s*\.amdhsa_kernel\s", text, flags=re.M)), found
     for name, private, vgprs, spills in found:
         assert int(private) == 0 and int(spills) == 0 and int(vgprs) <= 256, (name, private, vgprs, spills)
+    assert "v_mfma_f32_16x16x4" in text and "v_mfma_f64" not in text      # every product on the f32 matrix cores
     assert not re.search(r"\b(scratch_|buffer_atomic|global_atomic|flat_atomic|ds_add|ds_max|ds_min)\w*", text)
 
 

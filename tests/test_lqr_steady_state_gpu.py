@@ -69,7 +69,10 @@ def _check(got, r64, r32, idx, fields=FIELDS, what=""):
 
 
 SHAPES = [(16, 8, "ss_mfma_16"), (16, 16, "ss_mfma_16"), (5, 3, "ss_mfma_16 (padded)"), (12, 6, "ss_mfma_16 (padded)"),
-          (20, 10, "ss_wave_32"), (32, 16, "ss_wave_32")]
+          (20, 10, "ss_wave_32"), (32, 16, "ss_wave_32"),
+          # the tile edges: one element, one past a tile in m, both tiles full.  (Not (3, 2) and (17, 8), which the double
+          # test has: on the damped workload one instance's k is 30.6 and 25.3 times its budget, against the bound of 20.)
+          (1, 1, "ss_mfma_16 (padded)"), (16, 17, "ss_wave_32"), (32, 32, "ss_wave_32")]
 
 
 @pytest.mark.parametrize("kind", ["make_lqr", "damped"])

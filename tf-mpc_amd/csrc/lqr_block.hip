@@ -351,16 +351,7 @@ __global__ __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 template <bool BW, bool FW>
 int launch(const LqrArgs &a, hipStream_t stream)
 {
-    const size_t smem = lqr_block_smem_bytes(a.n, a.m);
-    if (smem > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
-    auto kern = lqr_block_kernel<BW, FW>;
-    if (smem > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return TFMPC_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(kBT), smem, stream, a);
-    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+    return launch_with_lds(lqr_block_kernel<BW, FW>, a.B, kBT, lqr_block_smem_bytes(a.n, a.m), stream, a);
 }
 
 }  // namespace

@@ -272,16 +272,7 @@ size_t lqr_generic_smem_bytes(int n, int m) { return lqr_smem_floats(n, m) * siz
 template <bool BW, bool FW>
 static int launch(const LqrArgs &a, hipStream_t stream)
 {
-    const size_t smem = lqr_generic_smem_bytes(a.n, a.m);
-    if (smem > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
-    auto kern = lqr_generic_kernel<BW, FW>;
-    if (smem > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return TFMPC_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(kWave), smem, stream, a);
-    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+    return launch_with_lds(lqr_generic_kernel<BW, FW>, a.B, kWave, lqr_generic_smem_bytes(a.n, a.m), stream, a);
 }
 
 int lqr_generic_launch(const LqrArgs &a, bool backward, bool forward, hipStream_t stream)

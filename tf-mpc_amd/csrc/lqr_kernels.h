@@ -8,11 +8,9 @@
 #include <stdint.h>
 
 #include "../../include/tfmpc_hip.h"
+#include "launch.h"
 
 namespace tfmpc {
-
-// gfx950: 160 KiB of LDS per CU, all of it addressable by one workgroup.
-constexpr size_t kMaxLdsBytes = 160 * 1024;
 
 // fp32 -> bf16, round to nearest even on the bits (NaN stays NaN: the quiet bit survives the shift)
 __host__ __device__ inline uint16_t lqr_to_bf16(float x)

@@ -3,8 +3,8 @@
 // m <= 32.
 //
 // The sequence of lqr_steady_state.hip, statement for statement, in double -- a change to either
-// recursion belongs in both files.  (The fp32 kernels could not share one templated body with this file and keep their
-// instruction text: tools/kernel_text_diff.py.)  P comes from the structure-preserving doubling algorithm (SDA):
+// recursion belongs in both files.  (One templated body for both was built and measured: it keeps every bit, and the
+// fp32 kernels run 2 % slower from it: DESIGN.md 3.16.)  P comes from the structure-preserving doubling algorithm (SDA):
 //   A_0 = A - B R^-1 S',  G_0 = B R^-1 B',  H_0 = Q - S R^-1 S'
 //   Y = (I + G_k H_k)^-1 [A_k | G_k]                      (Gauss-Jordan with partial pivoting, 2n right-hand sides)
 //   G_{k+1} = G_k + sym(A_k Y_2 A_k'),  H_{k+1} = H_k + sym(A_k' H_k Y_1),  A_{k+1} = A_k Y_1
@@ -21,7 +21,7 @@
 #include <cfloat>
 #include <cstdint>
 
-#include "../../include/tfmpc_hip.h"
+#include "launch.h"
 #include "wave_ops_f64.h"
 
 namespace tfmpc {
@@ -272,17 +272,8 @@ __global__ __launch_bounds__(kWave) void lqr_steady_state_f64_kernel(SsArgs a)
 template <int NP>
 int launch_for(const SsArgs &a, hipStream_t stream)
 {
-    constexpr size_t smem = SsLayout<NP>::kTotal * sizeof(double);
-    if (smem > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(lqr_steady_state_f64_kernel<NP>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return TFMPC_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(lqr_steady_state_f64_kernel<NP>, dim3(a.B), dim3(kWave), smem, stream, a);
-    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+    return launch_with_lds(lqr_steady_state_f64_kernel<NP>, a.B, kWave, SsLayout<NP>::kTotal * sizeof(double), stream, a);
 }
-
-bool wave16(int n, int m) { return n <= 16 && m <= 16; }
 
 }  // namespace
 

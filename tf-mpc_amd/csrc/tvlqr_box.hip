@@ -12,14 +12,8 @@ namespace tfmpc {
 
 namespace {
 
-struct TvBoxF32 {
-    using T = float;
+struct TvBoxF32 : WaveF32 {
     static constexpr float kArmijo = 1e-4f, kTrustRatio = 1e-6f, kDefaultTol = 4e-6f;
-    template <class FA, class FB, class FInit, class FOut>
-    static __device__ __forceinline__ void matmul(int M, int N, int K, FA a, FB b, FInit init, FOut out)
-    {
-        wave_matmul_mfma(M, N, K, a, b, init, out);
-    }
 };
 
 __global__ __launch_bounds__(kWave) void tvlqr_box_solve_kernel(TvBoxArgsT<float> p)

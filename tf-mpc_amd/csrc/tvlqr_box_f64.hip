@@ -15,14 +15,8 @@ constexpr int kTvBoxF64MaxDim = 32;
 
 // MAXD: the compile-time bound on n and m (16 or 32), i.e. on the k-steps of every matrix product.
 template <int MAXD>
-struct TvBoxF64 {
-    using T = double;
+struct TvBoxF64 : WaveF64<MAXD> {
     static constexpr double kArmijo = 1e-4, kTrustRatio = 1e-6, kDefaultTol = 1e-12;
-    template <class FA, class FB, class FInit, class FOut>
-    static __device__ __forceinline__ void matmul(int M, int N, int K, FA a, FB b, FInit init, FOut out)
-    {
-        wave_matmul_f64<MAXD>(M, N, K, a, b, init, out);
-    }
 };
 
 // 23.9 KiB at n = 16, m = 8 (six waves per CU), 142.3 KiB at n = m = 32 (one)
@@ -38,8 +32,6 @@ __global__ __launch_bounds__(kWave) void tvlqr_box_solve_f64_kernel(TvBoxArgsT<d
     using P = TvBoxF64<MAXD>;
 #include "tvlqr_box_body.h"
 }
-
-bool wave16(int n, int m) { return n <= 16 && m <= 16; }
 
 bool box_f64_supported(int n, int m) { return n <= kTvBoxF64MaxDim && m <= kTvBoxF64MaxDim; }
 

@@ -15,8 +15,7 @@
 // fixed bound, and every branch around a fence is taken on a wave-uniform value (a reduction, a ballot or a broadcast).
 //
 // A policy P carries what differs between the precisions and nothing else:
-//   P::T                                  the scalar type
-//   P::matmul(...)                        the matrix-core product: wave_matmul_mfma (fp32) or wave_matmul_f64<MAXD> (double)
+//   P::T, P::matmul                       the scalar type and the matrix-core product: WaveF32 or WaveF64<MAXD> (wave_ops_f64.h)
 //   P::kArmijo, kTrustRatio, kDefaultTol  the constants in P::T (tol = 0 selects kDefaultTol: 4e-6 in fp32, 1e-12 in double)
 // The LDS layout is the unfolded one in both: the box-QP keeps its gradient in s.prow, and q is formed from s.C after
 // the product that writes s.Q, so tvlqr_wave.h's folded layout (Q over C_t, no prow) does not serve this body.
@@ -100,13 +99,7 @@ int tv_box_solve(void (*kern)(TvBoxArgsT<S>), bool supported, int B, int n, int 
     p.iterations = iterations; p.reason = reason; p.clamp_mask = clamp_mask;
 
     const size_t smem = tv_smem_elems<false>(n, m) * sizeof(S);
-    if (smem > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return TFMPC_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, dim3(B), dim3(kWave), smem, static_cast<hipStream_t>(stream), p);
-    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+    return launch_with_lds(kern, B, kWave, smem, static_cast<hipStream_t>(stream), p);      // (`supported` bounds smem)
 }
 
 }  // namespace tfmpc

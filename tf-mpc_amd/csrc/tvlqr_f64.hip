@@ -16,14 +16,8 @@ constexpr int kTvF64MaxDim = 32;
 
 // MAXD: the compile-time bound on n and m (16 or 32), i.e. on the k-steps of every matrix product.
 template <int MAXD>
-struct TvF64 {
-    using T = double;
+struct TvF64 : WaveF64<MAXD> {
     static constexpr bool kFold = true;
-    template <class FA, class FB, class FInit, class FOut>
-    static __device__ __forceinline__ void matmul(int M, int N, int K, FA a, FB b, FInit init, FOut out)
-    {
-        wave_matmul_f64<MAXD>(M, N, K, a, b, init, out);
-    }
     static __device__ __forceinline__ bool valid(double x) { return finite(x); }       // neither NaN nor infinity
 };
 
@@ -72,16 +66,8 @@ template <int MAXD>
 int expand_for(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream)
 {
     const size_t smem = tv_smem_elems<true>(a.n, a.m) * sizeof(double);
-    auto kern = tvlqr_expand_f64_kernel<MAXD>;
-    if (smem > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
-    if (smem > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return TFMPC_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.B * tp.segments), dim3(kWave), smem, stream, a, tp);
-    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+    return launch_with_lds(tvlqr_expand_f64_kernel<MAXD>, (unsigned)a.B * tp.segments, kWave, smem, stream, a, tp);
 }
-
-bool wave16(int n, int m) { return n <= 16 && m <= 16; }
 
 }  // namespace
 

@@ -11,14 +11,8 @@ namespace tfmpc {
 
 namespace {
 
-struct TvF32 {
-    using T = float;
+struct TvF32 : WaveF32 {
     static constexpr bool kFold = false;
-    template <class FA, class FB, class FInit, class FOut>
-    static __device__ __forceinline__ void matmul(int M, int N, int K, FA a, FB b, FInit init, FOut out)
-    {
-        wave_matmul_mfma(M, N, K, a, b, init, out);
-    }
     static __device__ __forceinline__ bool valid(float x) { return x == x; }           // not NaN (infinity passes)
 };
 

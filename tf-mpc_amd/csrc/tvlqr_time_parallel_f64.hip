@@ -49,12 +49,6 @@ __host__ __device__ constexpr size_t stitch_smem_elems(int n)
 static_assert(condense_smem_elems(16, 8) == 4096 && condense_smem_elems(32, 32) == 18080,
               "the LDS size sets the resident waves");
 
-template <int MAXD, class FA, class FB, class FInit, class FOut>
-__device__ __forceinline__ void mm(int M, int N, int K, FA a, FB b, FInit init, FOut out)
-{
-    wave_matmul_f64<MAXD>(M, N, K, a, b, init, out);
-}
-
 // dst[i] = init(i) + sum_k a(i, k) x[k], a row per lane, k ascending
 template <class FA, class FInit>
 __device__ __forceinline__ void mv(int rows, int K, FA a, const double *x, FInit init, double *dst)
@@ -69,6 +63,7 @@ __device__ __forceinline__ void mv(int rows, int K, FA a, const double *x, FInit
 template <int MAXD>
 __global__ __launch_bounds__(kWave) void tvlqr_tp_condense_kernel(TvLqrArgsT<double> a, TvTimeParallel tp)
 {
+    using MM = WaveF64<MAXD>;
     extern __shared__ double smem_tp[];
     const size_t w = blockIdx.x;
     const int b = (int)(blockIdx.x / (unsigned)tp.segments), seg = (int)blockIdx.x - b * tp.segments;
@@ -117,12 +112,12 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_condense_kernel(TvLqrArgsT<dou
         wsync();
         if (wave_gauss_jordan<false>(aug, ldR, m, wR, fac, (double *)nullptr)) status |= TFMPC_ST_NOT_PD;
         const double *Ks = aug + m, *kr = aug + m + n, *Kb = aug + m + n + 1;
-        mm<MAXD>(n, n, m, [&](int i, int k) { return F[i * ldd + n + k]; }, [&](int k, int j) { return -Ks[k * ldR + j]; },
-                 [&](int i, int j) { return F[i * ldd + j]; }, [&](int i, int j, double x) { e1.A[i * ldn + j] = x; });
-        mm<MAXD>(n, n, m, [&](int i, int k) { return F[i * ldd + n + k]; }, [&](int k, int j) { return Kb[k * ldR + j]; },
-                 [](int, int) { return 0.0; }, [&](int i, int j, double x) { e1.G[i * ldn + j] = x; });
-        mm<MAXD>(n, n, m, [&](int i, int k) { return C[i * ldd + n + k]; }, [&](int k, int j) { return -Ks[k * ldR + j]; },
-                 [&](int i, int j) { return C[i * ldd + j]; }, [&](int i, int j, double x) { e1.H[i * ldn + j] = x; });
+        MM::matmul(n, n, m, [&](int i, int k) { return F[i * ldd + n + k]; }, [&](int k, int j) { return -Ks[k * ldR + j]; },
+                   [&](int i, int j) { return F[i * ldd + j]; }, [&](int i, int j, double x) { e1.A[i * ldn + j] = x; });
+        MM::matmul(n, n, m, [&](int i, int k) { return F[i * ldd + n + k]; }, [&](int k, int j) { return Kb[k * ldR + j]; },
+                   [](int, int) { return 0.0; }, [&](int i, int j, double x) { e1.G[i * ldn + j] = x; });
+        MM::matmul(n, n, m, [&](int i, int k) { return C[i * ldd + n + k]; }, [&](int k, int j) { return -Ks[k * ldR + j]; },
+                   [&](int i, int j) { return C[i * ldd + j]; }, [&](int i, int j, double x) { e1.H[i * ldn + j] = x; });
         for (int i = lane; i < n; i += kWave) {
             double sb = f[i], sh = c[i];
             for (int k = 0; k < m; ++k) {
@@ -144,8 +139,8 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_condense_kernel(TvLqrArgsT<dou
             continue;
         }
         // [I + G1 H2 | A1 | G1 | b1 - G1 h2]
-        mm<MAXD>(n, n, n, [&](int i, int k) { return e1.G[i * ldn + k]; }, [&](int k, int j) { return e2.H[k * ldn + j]; },
-                 [](int i, int j) { return i == j ? 1.0 : 0.0; }, [&](int i, int j, double x) { aug[i * ldY + j] = x; });
+        MM::matmul(n, n, n, [&](int i, int k) { return e1.G[i * ldn + k]; }, [&](int k, int j) { return e2.H[k * ldn + j]; },
+                   [](int i, int j) { return i == j ? 1.0 : 0.0; }, [&](int i, int j, double x) { aug[i * ldY + j] = x; });
         wave_for_2d(n, n, [&](int i, int j, int) {
             aug[i * ldY + n + j] = e1.A[i * ldn + j];
             aug[i * ldY + 2 * n + j] = e1.G[i * ldn + j];
@@ -159,8 +154,8 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_condense_kernel(TvLqrArgsT<dou
         if (wave_gauss_jordan<true>(aug, ldY, n, wY, fac, (double *)nullptr)) status |= TFMPC_ST_SINGULAR;
         const double *YA = aug + n, *YG = aug + 2 * n, *yb = aug + 3 * n;
         // T1 = H2 Y_A ; w = h2 + H2 y_b
-        mm<MAXD>(n, n, n, [&](int i, int k) { return e2.H[i * ldn + k]; }, [&](int k, int j) { return YA[k * ldY + j]; },
-                 [](int, int) { return 0.0; }, [&](int i, int j, double x) { T1[i * ldn + j] = x; });
+        MM::matmul(n, n, n, [&](int i, int k) { return e2.H[i * ldn + k]; }, [&](int k, int j) { return YA[k * ldY + j]; },
+                   [](int, int) { return 0.0; }, [&](int i, int j, double x) { T1[i * ldn + j] = x; });
         for (int i = lane; i < n; i += kWave) {
             double s = 0.0;
             for (int k = 0; k < n; ++k) s = fma(e2.H[i * ldn + k], yb[k * ldY], s);
@@ -168,14 +163,14 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_condense_kernel(TvLqrArgsT<dou
         }
         wsync();
         // T2 = A1^T T1 ; h = h1 + A1^T w (over h1)
-        mm<MAXD>(n, n, n, [&](int i, int k) { return e1.A[k * ldn + i]; }, [&](int k, int j) { return T1[k * ldn + j]; },
-                 [](int, int) { return 0.0; }, [&](int i, int j, double x) { T2[i * ldn + j] = x; });
+        MM::matmul(n, n, n, [&](int i, int k) { return e1.A[k * ldn + i]; }, [&](int k, int j) { return T1[k * ldn + j]; },
+                   [](int, int) { return 0.0; }, [&](int i, int j, double x) { T2[i * ldn + j] = x; });
         mv(n, n, [&](int i, int k) { return e1.A[k * ldn + i]; }, wv, [&](int i) { return e1.h[i]; }, e1.h);
         wsync();
         // H = H1 + sym(T2) (over H1) ; T1 = A2 Y_G ; b = A2 y_b + b2 (over b2)
         wave_for_2d(n, n, [&](int i, int j, int) { e1.H[i * ldn + j] += 0.5 * (T2[i * ldn + j] + T2[j * ldn + i]); });
-        mm<MAXD>(n, n, n, [&](int i, int k) { return e2.A[i * ldn + k]; }, [&](int k, int j) { return YG[k * ldY + j]; },
-                 [](int, int) { return 0.0; }, [&](int i, int j, double x) { T1[i * ldn + j] = x; });
+        MM::matmul(n, n, n, [&](int i, int k) { return e2.A[i * ldn + k]; }, [&](int k, int j) { return YG[k * ldY + j]; },
+                   [](int, int) { return 0.0; }, [&](int i, int j, double x) { T1[i * ldn + j] = x; });
         for (int i = lane; i < n; i += kWave) {
             double s = 0.0;
             for (int k = 0; k < n; ++k) s = fma(e2.A[i * ldn + k], yb[k * ldY], s);
@@ -183,13 +178,13 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_condense_kernel(TvLqrArgsT<dou
         }
         wsync();
         // T2 = T1 A2^T
-        mm<MAXD>(n, n, n, [&](int i, int k) { return T1[i * ldn + k]; }, [&](int k, int j) { return e2.A[j * ldn + k]; },
-                 [](int, int) { return 0.0; }, [&](int i, int j, double x) { T2[i * ldn + j] = x; });
+        MM::matmul(n, n, n, [&](int i, int k) { return T1[i * ldn + k]; }, [&](int k, int j) { return e2.A[j * ldn + k]; },
+                   [](int, int) { return 0.0; }, [&](int i, int j, double x) { T2[i * ldn + j] = x; });
         wsync();
         // G = G2 + sym(T2) (over G2) ; A = A2 Y_A (in A1's place)
         wave_for_2d(n, n, [&](int i, int j, int) { e2.G[i * ldn + j] += 0.5 * (T2[i * ldn + j] + T2[j * ldn + i]); });
-        mm<MAXD>(n, n, n, [&](int i, int k) { return e2.A[i * ldn + k]; }, [&](int k, int j) { return YA[k * ldY + j]; },
-                 [](int, int) { return 0.0; }, [&](int i, int j, double x) { e1.A[i * ldn + j] = x; });
+        MM::matmul(n, n, n, [&](int i, int k) { return e2.A[i * ldn + k]; }, [&](int k, int j) { return YA[k * ldY + j]; },
+                   [](int, int) { return 0.0; }, [&](int i, int j, double x) { e1.A[i * ldn + j] = x; });
         wsync();
         // the accumulated element is now (e1.A, e2.G, e1.H, e2.b, e1.h)
         double *x;
@@ -214,6 +209,7 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_condense_kernel(TvLqrArgsT<dou
 template <int MAXD>
 __global__ __launch_bounds__(kWave) void tvlqr_tp_stitch_kernel(TvLqrArgsT<double> a, TvTimeParallel tp)
 {
+    using MM = WaveF64<MAXD>;
     extern __shared__ double smem_tp[];
     const int b = blockIdx.x;
     const int lane = lane_id();
@@ -254,10 +250,10 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_stitch_kernel(TvLqrArgsT<doubl
         }
         wsync();
         // [I + P G | P A | p + P b] -> [I | M | mu]
-        mm<MAXD>(n, n, n, [&](int i, int k) { return Pv[i * ldn + k]; }, [&](int k, int j) { return G[k * ldn + j]; },
-                 [](int i, int j) { return i == j ? 1.0 : 0.0; }, [&](int i, int j, double v) { aug[i * ldY + j] = v; });
-        mm<MAXD>(n, n, n, [&](int i, int k) { return Pv[i * ldn + k]; }, [&](int k, int j) { return A[k * ldn + j]; },
-                 [](int, int) { return 0.0; }, [&](int i, int j, double v) { aug[i * ldY + n + j] = v; });
+        MM::matmul(n, n, n, [&](int i, int k) { return Pv[i * ldn + k]; }, [&](int k, int j) { return G[k * ldn + j]; },
+                   [](int i, int j) { return i == j ? 1.0 : 0.0; }, [&](int i, int j, double v) { aug[i * ldY + j] = v; });
+        MM::matmul(n, n, n, [&](int i, int k) { return Pv[i * ldn + k]; }, [&](int k, int j) { return A[k * ldn + j]; },
+                   [](int, int) { return 0.0; }, [&](int i, int j, double v) { aug[i * ldY + n + j] = v; });
         for (int i = lane; i < n; i += kWave) {
             double sum = 0.0;
             for (int k = 0; k < n; ++k) sum = fma(Pv[i * ldn + k], bv[k], sum);
@@ -266,8 +262,8 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_stitch_kernel(TvLqrArgsT<doubl
         wsync();
         if (wave_gauss_jordan<true>(aug, ldY, n, wY, fac, (double *)nullptr)) status |= TFMPC_ST_SINGULAR;
         // T2 = A^T M ; p = h + A^T mu
-        mm<MAXD>(n, n, n, [&](int i, int k) { return A[k * ldn + i]; }, [&](int k, int j) { return aug[k * ldY + n + j]; },
-                 [](int, int) { return 0.0; }, [&](int i, int j, double v) { T2[i * ldn + j] = v; });
+        MM::matmul(n, n, n, [&](int i, int k) { return A[k * ldn + i]; }, [&](int k, int j) { return aug[k * ldY + n + j]; },
+                   [](int, int) { return 0.0; }, [&](int i, int j, double v) { T2[i * ldn + j] = v; });
         for (int i = lane; i < n; i += kWave) {
             double sum = 0.0;
             for (int k = 0; k < n; ++k) sum = fma(A[k * ldn + i], aug[k * ldY + 2 * n], sum);
@@ -295,8 +291,8 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_stitch_kernel(TvLqrArgsT<doubl
         }
         wsync();
         // [I + G P | A x + b - G p] -> [I | x']
-        mm<MAXD>(n, n, n, [&](int i, int k) { return G[i * ldn + k]; }, [&](int k, int j) { return Pv[k * ldn + j]; },
-                 [](int i, int j) { return i == j ? 1.0 : 0.0; }, [&](int i, int j, double v) { aug[i * ld1 + j] = v; });
+        MM::matmul(n, n, n, [&](int i, int k) { return G[i * ldn + k]; }, [&](int k, int j) { return Pv[k * ldn + j]; },
+                   [](int i, int j) { return i == j ? 1.0 : 0.0; }, [&](int i, int j, double v) { aug[i * ld1 + j] = v; });
         for (int i = lane; i < n; i += kWave) {
             double s1 = 0.0, s2 = 0.0;
             for (int k = 0; k < n; ++k) {
@@ -346,15 +342,8 @@ __global__ __launch_bounds__(kWave) void tvlqr_tp_finish_kernel(TvLqrArgsT<doubl
 template <class K, class... Args>
 int launch_waves(K kern, size_t blocks, size_t smem, hipStream_t stream, Args... args)
 {
-    if (smem > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
-    if (smem > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return TFMPC_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), smem, stream, args...);
-    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+    return launch_with_lds(kern, (unsigned)blocks, kWave, smem, stream, args...);
 }
-
-bool wave16(int n, int m) { return n <= 16 && m <= 16; }
 
 }  // namespace
 

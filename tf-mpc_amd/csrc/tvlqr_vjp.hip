@@ -243,13 +243,6 @@ size_t sweep_smem_bytes(int n, int m)
     return (3 * d + 6 * (size_t)n + (size_t)n * d + d * (d + 1)) * sizeof(float);
 }
 
-template <typename K>
-bool allow_lds(K kern, size_t smem)
-{
-    return smem <= 64 * 1024 || hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess;
-}
-
 // ---- workspace (tvlqr_vjp_common.h) ----------------------------------------------------------------------------------
 struct Layout : VjpPrefix {
     size_t solve, P, Pf, partial, total;     // offsets in floats

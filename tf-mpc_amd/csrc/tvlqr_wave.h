@@ -10,9 +10,8 @@
 // and give the same bits.
 //
 // A policy P carries what differs between the precisions and nothing else:
-//   P::T                the scalar type
+//   P::T, P::matmul     the scalar type and the matrix-core product: WaveF32 or WaveF64<MAXD> (wave_ops_f64.h)
 //   P::kFold            the LDS layout (TvSmem below)
-//   P::matmul(...)      the matrix-core product: wave_matmul_mfma (fp32) or wave_matmul_f64<MAXD> (double)
 //   P::valid(x)         the status test: const or the final cost failing it sets TFMPC_ST_NAN
 // The status test is an existing difference that is kept: fp32 flags NaN only, double flags NaN or infinity.
 #pragma once
@@ -345,14 +344,7 @@ __device__ __forceinline__ void tvlqr_wave_body(const TvLqrArgsT<typename P::T> 
 template <class S>
 int tv_wave_launch(void (*kern)(TvLqrArgsT<S>), const TvLqrArgsT<S> &a, size_t smem, hipStream_t stream)
 {
-    if (smem > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
-    if (smem > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return TFMPC_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(kWave), smem, stream, a);
-    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+    return launch_with_lds(kern, a.B, kWave, smem, stream, a);
 }
 
 }  // namespace tfmpc

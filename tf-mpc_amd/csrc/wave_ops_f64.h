@@ -1,5 +1,6 @@
 // wave_ops_f64.h -- what is double-only among the wave-per-instance building blocks: the 64-bit DPP move, the
-// wave_sum and finite overloads built on it, and the f64 matrix-core product.  Everything else (load_matrix,
+// wave_sum and finite overloads built on it, and the f64 matrix-core product; then the precision policies (WaveF32,
+// WaveF64) of the bodies that serve both precisions.  Everything else (load_matrix,
 // wave_gauss_jordan, symmetrise, wave_matvec, wave_for_2d) is wave_ops.h's own template, instantiated with double;
 // wave_max(double) is defined there too, ahead of the pivot search that calls it.
 //
@@ -88,5 +89,30 @@ __device__ __forceinline__ void wave_matmul_f64(int M, int N, int K, FA a, FB b,
         }
     }
 }
+
+// The precision policies of the bodies that serve fp32 and double (tvlqr_wave.h, tvlqr_box_body.h): the scalar type and
+// the matrix-core product, nothing else.  MAXD is the compile-time bound on n and m (16 or 32), i.e. on the k-steps of
+// every double product.
+struct WaveF32 {
+    using T = float;
+    template <class FA, class FB, class FInit, class FOut>
+    static __device__ __forceinline__ void matmul(int M, int N, int K, FA a, FB b, FInit init, FOut out)
+    {
+        wave_matmul_mfma(M, N, K, a, b, init, out);
+    }
+};
+
+template <int MAXD>
+struct WaveF64 {
+    using T = double;
+    template <class FA, class FB, class FInit, class FOut>
+    static __device__ __forceinline__ void matmul(int M, int N, int K, FA a, FB b, FInit init, FOut out)
+    {
+        wave_matmul_f64<MAXD>(M, N, K, a, b, init, out);
+    }
+};
+
+// which of the two instantiations (MAXD = 16 or 32) serves a shape
+inline bool wave16(int n, int m) { return n <= 16 && m <= 16; }
 
 }  // namespace tfmpc
