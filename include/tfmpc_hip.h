@@ -387,6 +387,38 @@ int tfmpc_tvlqr_box_vjp_f32(int B, int n, int m, int T,
                             float *dlow, long sdlow_b, long sdlow_t, float *dhigh, long sdhigh_b, long sdhigh_t,
                             uint32_t *clamp_mask, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------- control-limited TV-LQR gradients, double precision --------
+ * tfmpc_tvlqr_box_vjp_f32's contract with every value a double: the same argument list in the same
+ * order, strides in ELEMENTS, the held set read off the actions' DOUBLE bits (low when a control equals both bounds, no
+ * multiplier test), the same outputs, stride-0 sums in a fixed order without atomics, exact zeros in dlow / dhigh off the
+ * held set and on the other bound, clamp_mask, B == 0 a no-op, the same checks in the same order before any launch.  The
+ * costates are NOT that call's open-loop recursion but tfmpc_tvlqr_vjp_f64's value-function form on the REDUCED problem
+ * (held controls fixed at their bounds): lam_t = V^m_t x_t + v^m_t, dlam_t = V^m_t dx_t + v~_t, with V^m, v~ from the
+ * adjoint sweep on the masked model and v^m from a second masked backward sweep with the linear terms
+ * f_t + F_t[:, n + H_t] u_H, c_t + C_t[:, n + H_t] u_H and the true final cost; no input beyond the f32 call's is needed.
+ * status[B] (required) gets the OR of both sweeps' status words; an instance with any bit set has NaN in its own gradient
+ * rows, dlow / dhigh included, and in every batch-summed gradient.  n <= 32 and m <= 32 (kernel_name:
+ * "tv_masked_f64_wave16" for n <= 16 and m <= 16, "tv_masked_f64_wave32" otherwise; "unsupported" beyond, "invalid" for
+ * n <= 0 or m <= 0), TFMPC_ERR_UNSUPPORTED beyond.  With up(x) = x rounded up to a multiple of 64, d = n + m and
+ * chunks = ceil(B / 256), the workspace holds tfmpc_tvlqr_vjp_workspace_bytes_f64(B, n, m, T) plus
+ *   8 * [ up(ceil(B T / 2)) + up(ceil(B / 2)) + 3 up(B T m) + 2 up(B T n) + up(B T d) ]  bytes
+ * (held-set words, the second sweep's status, the unmasked g_u and the two bound records, f^ and v^m, c^); 0 for B <= 0.
+ * The workspace must be 8-byte aligned (TFMPC_ERR_ARG otherwise, after the size check): doubles are carved from it. */
+size_t tfmpc_tvlqr_box_vjp_workspace_bytes_f64(int B, int n, int m, int T);
+const char *tfmpc_tvlqr_box_vjp_kernel_name_f64(int n, int m, int T);
+int tfmpc_tvlqr_box_vjp_f64(int B, int n, int m, int T,
+                            const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                            const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                            const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                            const double *low, long slow_b, long slow_t, const double *high, long shigh_b, long shigh_t,
+                            const double *states, const double *actions,
+                            const double *g_states, const double *g_actions, const double *g_costs,
+                            double *dF, long sdF_b, long sdF_t, double *df, long sdf_b, long sdf_t,
+                            double *dC, long sdC_b, long sdC_t, double *dc, long sdc_b, long sdc_t,
+                            double *dCfin, long sdCfin_b, double *dcfin, long sdcfin_b, double *dx0, long sdx0_b,
+                            double *dlow, long sdlow_b, long sdlow_t, double *dhigh, long sdhigh_b, long sdhigh_t,
+                            uint32_t *clamp_mask, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------ control-limited TV-LQR, the solve --------
  * The forward of tfmpc_tvlqr_box_vjp_f32: the optimum of the TV-LQR problem under low <= u_t <= high.
  * Model operands, Cfin / cfin and their strides as in tfmpc_tvlqr_solve_f32; low, high as in tfmpc_tvlqr_box_vjp_f32
@@ -434,7 +466,7 @@ int tfmpc_tvlqr_box_solve_f32(int B, int n, int m, int T,
  * "tv_box_f64_wave32" otherwise; "unsupported" beyond, "invalid" for n <= 0 or m <= 0), TFMPC_ERR_UNSUPPORTED beyond.
  * workspace: tfmpc_tvlqr_box_solve_workspace_bytes_f64(B, n, m, T) = 8 B (T m (n + 1) + (T + 1) n + T m + T + 1) bytes, 0
  * for B <= 0.  The same argument, shape and workspace checks in the same order; B == 0 is a no-op.  A control on a
- * bound carries the double bound's bits.  There is no double VJP: tfmpc_tvlqr_box_vjp_f32 is the only gradient. */
+ * bound carries the double bound's bits, which is what tfmpc_tvlqr_box_vjp_f64's held-set rule reads. */
 size_t tfmpc_tvlqr_box_solve_workspace_bytes_f64(int B, int n, int m, int T);
 const char *tfmpc_tvlqr_box_solve_kernel_name_f64(int n, int m, int T);
 int tfmpc_tvlqr_box_solve_f64(int B, int n, int m, int T,

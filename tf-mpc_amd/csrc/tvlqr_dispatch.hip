@@ -93,7 +93,7 @@ int forward(int B, int n, int m, int T, const Model<S> &md, const S *K, long str
     return launch(a, false, true, static_cast<hipStream_t>(stream));
 }
 
-// mask != NULL: the masked sweep (fp32 only, tvlqr_solve_masked_f32)
+// mask != NULL: the masked sweep (fp32: tvlqr_solve_masked_f32; double has its own entry, tvlqr_solve_masked_f64)
 template <class S>
 int solve(int B, int n, int m, int T, const Model<S> &md, const S *x0, S *states, S *actions, S *costs, S *K, S *k,
           S *V, S *v, S *cst, int32_t *status, const uint32_t *mask, void *workspace, size_t workspace_bytes_given,
@@ -157,6 +157,26 @@ int tvlqr_solve_masked_f32(TFMPC_TVLQR_MODEL_PARAMS(float), const float *x0, flo
 {
     return solve<float>(TFMPC_TVLQR_MODEL(float), x0, states, actions, costs, nullptr, nullptr, nullptr, nullptr, nullptr,
                         status, mask, workspace, workspace_bytes, stream);
+}
+
+int tvlqr_solve_masked_f64(TFMPC_TVLQR_MODEL_PARAMS(double), const double *x0, double *states, double *actions,
+                           double *costs, double *V, double *v, int32_t *status, const uint32_t *mask, void *workspace,
+                           size_t workspace_bytes_given, void *stream)
+{
+    const Model<double> md{F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b};
+    int rc = check_model(B, n, m, T, md);
+    if (rc != TFMPC_OK || B == 0) return rc;
+    const bool forward = states != nullptr;
+    if (!mask || (forward && (!x0 || !actions || !costs))) return TFMPC_ERR_ARG;
+    if (!workspace || workspace_bytes_given < workspace_bytes<double>(B, n, m, T)) return TFMPC_ERR_WORKSPACE;
+    double *w = static_cast<double *>(workspace);
+    TvLqrArgsT<double> a = make_args(B, n, m, T, md);
+    a.x0 = x0;
+    a.K = w; a.k = w + (size_t)B * T * m * n; a.sK = (long)T * m * n; a.sk = (long)T * m;
+    a.V = V; a.v = v;
+    a.states = states; a.actions = actions; a.costs = costs; a.status = status;
+    a.mask = mask;
+    return tvlqr_f64_masked_launch(a, forward, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace tfmpc

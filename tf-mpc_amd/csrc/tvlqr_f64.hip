@@ -69,6 +69,23 @@ int expand_for(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_
     return launch_with_lds(tvlqr_expand_f64_kernel<MAXD>, (unsigned)a.B * tp.segments, kWave, smem, stream, a, tp);
 }
 
+// The masked sweep (tvlqr_solve_masked_f64): the body with the held controls taken out of each step's
+// model; FORWARD = false is the backward sweep alone, for a caller that wants the value function only.
+template <int MAXD, bool FORWARD>
+__global__ __launch_bounds__(kWave) void tvlqr_masked_f64_sweep(TvLqrArgsT<double> a)
+{
+    extern __shared__ double smem_f64[];
+    tvlqr_wave_body<TvF64<MAXD>, true, FORWARD, true>(a, smem_f64);
+}
+
+template <int MAXD>
+int masked_for(const TvLqrArgsT<double> &a, bool forward, hipStream_t stream)
+{
+    const size_t smem = tv_smem_elems<true>(a.n, a.m) * sizeof(double);
+    if (forward) return tv_wave_launch(tvlqr_masked_f64_sweep<MAXD, true>, a, smem, stream);
+    return tv_wave_launch(tvlqr_masked_f64_sweep<MAXD, false>, a, smem, stream);
+}
+
 }  // namespace
 
 bool tvlqr_f64_supported(int n, int m) { return n <= kTvF64MaxDim && m <= kTvF64MaxDim; }
@@ -78,6 +95,13 @@ const char *tvlqr_f64_kernel_name(int n, int m) { return wave16(n, m) ? "tv_f64_
 int tvlqr_f64_launch(const TvLqrArgsT<double> &a, bool backward, bool forward, hipStream_t stream)
 {
     return wave16(a.n, a.m) ? launch_for<16>(a, backward, forward, stream) : launch_for<32>(a, backward, forward, stream);
+}
+
+const char *tvlqr_f64_masked_kernel_name(int n, int m) { return wave16(n, m) ? "tv_masked_f64_wave16" : "tv_masked_f64_wave32"; }
+
+int tvlqr_f64_masked_launch(const TvLqrArgsT<double> &a, bool forward, hipStream_t stream)
+{
+    return wave16(a.n, a.m) ? masked_for<16>(a, forward, stream) : masked_for<32>(a, forward, stream);
 }
 
 int tvlqr_f64_expand_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream)

@@ -26,7 +26,7 @@ struct TvLqrArgsT {
     S *V, *v, *cst;               // optional value-function outputs [B][T][n][n], [B][T][n], [B][T]
     S *states, *actions, *costs;
     int32_t *status;
-    const uint32_t *mask;         // [B][T] or NULL; bit i: control i is held at step t (masked sweep); fp32 only
+    const uint32_t *mask;         // [B][T] or NULL; bit i: control i is held at step t (masked sweep)
 };
 using TvLqrArgs = TvLqrArgsT<float>;
 
@@ -75,5 +75,17 @@ int tvlqr_solve_masked_f32(int B, int n, int m, int T, const float *F, long sF_b
                            const float *Cfin, long sCfin_b, const float *cfin, long scfin_b, const float *x0,
                            float *states, float *actions, float *costs, int32_t *status, const uint32_t *mask,
                            void *workspace, size_t workspace_bytes, void *stream);
+
+// The same in double, n <= 32 and m <= 32, which also hands out the masked problem's value function:
+// V[B][T][n][n], v[B][T][n] (each optional).  states == NULL runs the backward sweep alone (x0, actions, costs are then
+// not read or written).  The gains go to the workspace, tfmpc_tvlqr_workspace_bytes_f64.  The kernel's name is
+// "tv_masked_f64_wave16" or "tv_masked_f64_wave32".
+const char *tvlqr_f64_masked_kernel_name(int n, int m);
+int tvlqr_f64_masked_launch(const TvLqrArgsT<double> &a, bool forward, hipStream_t stream);
+int tvlqr_solve_masked_f64(int B, int n, int m, int T, const double *F, long sF_b, long sF_t, const double *f, long sf_b,
+                           long sf_t, const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                           const double *Cfin, long sCfin_b, const double *cfin, long scfin_b, const double *x0,
+                           double *states, double *actions, double *costs, double *V, double *v, int32_t *status,
+                           const uint32_t *mask, void *workspace, size_t workspace_bytes, void *stream);
 
 }  // namespace tfmpc

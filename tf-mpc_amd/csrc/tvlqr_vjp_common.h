@@ -13,7 +13,7 @@
 //   fp32:  P [B][T][2n], Pf [B][n], partial
 //   fp64:  V [B][T][n][n], vt [B][T][n], P [B][T][2n], partial
 // with partial [chunks][T][E], E = n d + n + d d + d (>= chunks n n of the final-cost sums); the control-limited VJP
-// appends mask [B][T], Rlo and Rhi [B][T][m].
+// appends mask [B][T], Rlo and Rhi [B][T][m] (fp32; the double one, tvlqr_box_vjp_f64.hip, states its own tail there).
 //
 // The build is -ffp-contract=off: every fused multiply-add is a written fma().
 #pragma once
@@ -63,8 +63,9 @@ struct VjpBase {
     int32_t poison_mask;             // the status bits of the adjoint solve that make an instance NaN
 };
 
-// The control-limited VJP's extra operands (fp32 only).  Rlo doubles as the fold's record of the unmasked g_u (read by
-// the sweep before it overwrites the entry with the bound's gradient).
+// The control-limited VJP's extra operands.  fp32: Rlo doubles as the fold's record of the unmasked g_u (read by the
+// sweep before it overwrites the entry with the bound's gradient); the double VJP (tvlqr_box_vjp_f64.hip) hands the fold
+// a record of its own in Rlo's place.
 template <class S>
 struct BoxArgsT {
     const S *low, *high;
@@ -75,6 +76,7 @@ struct BoxArgsT {
 };
 
 __device__ inline bool same_bits(float x, float y) { return __float_as_uint(x) == __float_as_uint(y); }
+__device__ inline bool same_bits(double x, double y) { return __double_as_longlong(x) == __double_as_longlong(y); }
 
 template <class S>
 __device__ inline S poison_of(const int32_t *status, int32_t mask, int b)

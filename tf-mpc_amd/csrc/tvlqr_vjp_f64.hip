@@ -62,6 +62,9 @@ __host__ __device__ inline size_t costate_smem_elems(int n, int m)
     return (size_t)n * (n + 1) + 4 * (size_t)n + 2 * (size_t)(n + m);
 }
 
+// KEEP IN STEP: tvlqr_box_vjp_f64.hip's box_costate_kernel is this kernel with the bounds' gradient added (a copy, so
+// that this file's kernels keep their text).  A change to the arithmetic here belongs there too: with no
+// control held the two must give the same bits (tests/test_tvlqr_box_grad_f64_gpu.py).
 // want: bit k = emit output k here.  LOOP = false: grid B T, block (b, t), every emitted output has its own slot per
 // step (or T == 1).  LOOP = true: grid B, the block walks the steps backwards and accumulates in the output.
 template <bool LOOP>

@@ -111,13 +111,12 @@ struct TvSegment {
     int32_t *status;              // this wave's own status word
 };
 
-// MASKED (DESIGN.md 3.11, fp32 only): held controls (bit i of a.mask[b][t]) are taken out of the step's model after the
-// LDS copy.
+// MASKED (in double 3.20): held controls (bit i of a.mask[b][t]) are taken out of the step's model after
+// the LDS copy.
 template <class P, bool BACKWARD, bool FORWARD, bool MASKED, class SEG = TvWhole>
 __device__ __forceinline__ void tvlqr_wave_body(const TvLqrArgsT<typename P::T> &a, typename P::T *smem, const SEG &seg = SEG())
 {
     using S = typename P::T;
-    static_assert(!MASKED || sizeof(S) == sizeof(float), "the masked sweep is fp32 only");
     static_assert(!MASKED || !SEG::kSegment, "the masked sweep runs whole horizons");
     int b;
     if constexpr (SEG::kSegment) b = seg.b;

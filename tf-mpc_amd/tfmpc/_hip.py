@@ -73,6 +73,11 @@ _SIGNATURES.update({
     # clamp_mask after dx0
     "tfmpc_tvlqr_box_vjp_f32": (_I, _TV_MODEL + [_P, _L, _L] * 2 + [_P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3
                                 + [_P, _L, _L] * 2 + [_P] + [_P, _P, _Z, _P]),
+    # ... in double: the same arguments, every float * a double *
+    "tfmpc_tvlqr_box_vjp_workspace_bytes_f64": (_Z, [_I, _I, _I, _I]),
+    "tfmpc_tvlqr_box_vjp_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I]),
+    "tfmpc_tvlqr_box_vjp_f64": (_I, _TV_MODEL + [_P, _L, _L] * 2 + [_P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3
+                                + [_P, _L, _L] * 2 + [_P] + [_P, _P, _Z, _P]),
     "tfmpc_tvlqr_box_solve_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "tfmpc_tvlqr_box_solve_kernel_name": (ctypes.c_char_p, [_I, _I, _I]),
     # low high (+ batch, time strides), x0, u_init (+ batch stride), max_iter tol, states actions costs, iterations status

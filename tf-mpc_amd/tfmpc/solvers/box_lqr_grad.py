@@ -20,10 +20,10 @@ from tfmpc.solvers.tvlqr_grad import as_f32_graph, wants_grad
 NAMES = ("F", "f", "C", "c", "C_final", "c_final", "x0", "low", "high")
 
 
-def _f32(a, device):
+def _cast(a, device, dtype=torch.float32):
     if isinstance(a, torch.Tensor):
-        return a.detach().to(device=device, dtype=torch.float32)
-    return torch.as_tensor(np.asarray(a, dtype=np.float32), device=device)
+        return a.detach().to(device=device, dtype=dtype)
+    return torch.as_tensor(np.asarray(a, dtype=np.float64 if dtype == torch.float64 else np.float32), device=device)
 
 
 def _timed(t, inner, name, B, T):
@@ -53,7 +53,7 @@ def _bound(t, m, name, B, T):
 
 
 def tvlqr_box_vjp(F, f, C, c, low, high, states, actions, g_states=None, g_actions=None, g_costs=None, C_final=None,
-                  c_final=None, want=None):
+                  c_final=None, want=None, dtype=None):
     """Vector-Jacobian product of a control-limited time-varying LQR solution.
 
     ``states[B, T+1, n]`` (``states[:, 0]`` is ``x0``) and ``actions[B, T, m]`` are the optimum of the problem of
@@ -65,11 +65,20 @@ def tvlqr_box_vjp(F, f, C, c, low, high, states, actions, g_states=None, g_actio
     in the operand's own shape -- an operand without a batch axis gets the sum over the batch, a time axis of 1 the sum
     over time; the default final cost's gradient is part of ``C``'s and ``c``'s -- plus ``"clamped"`` (bool
     ``[B, T, m]``: the held set) and ``"status"`` (``[B]``: the adjoint solve's).  An instance whose adjoint is not
-    positive definite gets NaN in its own rows and in every sum that contains it."""
+    positive definite gets NaN in its own rows and in every sum that contains it.
+
+    ``dtype``: ``None`` or ``torch.float32`` is ``tfmpc_tvlqr_box_vjp_f32``; float64 inputs are cast to fp32.
+    ``torch.float64`` keeps operands, bounds, the trajectory and the upstream gradients in double, with no pass through
+    fp32, runs ``tfmpc_tvlqr_box_vjp_f64`` (n <= 32, value-function costates, the held set read off
+    the actions' double bits) and returns float64 gradients; ``"status"`` is then the OR of both masked sweeps'."""
+    if dtype not in (None, torch.float32, torch.float64):
+        raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype!r}")
+    dt = torch.float64 if dtype == torch.float64 else torch.float32
+    size = 8 if dt == torch.float64 else 4
     lib = _hip.require_gpu()
     dev = next((t.device for t in (states, actions, F) if isinstance(t, torch.Tensor) and t.device.type != "cpu"),
                _hip.default_device())
-    states, actions = _f32(states, dev), _f32(actions, dev)
+    states, actions = _cast(states, dev, dt), _cast(actions, dev, dt)
     if states.dim() == 4:
         states = states.squeeze(-1)
     if actions.dim() == 4:
@@ -87,11 +96,11 @@ def tvlqr_box_vjp(F, f, C, c, low, high, states, actions, g_states=None, g_actio
         raise ValueError("give both C_final and c_final, or neither")
     ops = {}
     for name, a, inner in (("F", F, (n, d)), ("f", f, (n,)), ("C", C, (d, d)), ("c", c, (d,))):
-        ops[name] = _timed(_f32(a, dev), inner, name, B, T)
+        ops[name] = _timed(_cast(a, dev, dt), inner, name, B, T)
     for name, a in (("low", low), ("high", high)):
-        ops[name] = _bound(_f32(a, dev), m, name, B, T)
+        ops[name] = _bound(_cast(a, dev, dt), m, name, B, T)
     if C_final is not None:
-        Cf, cf = _f32(C_final, dev), _f32(c_final, dev)
+        Cf, cf = _cast(C_final, dev, dt), _cast(c_final, dev, dt)
         if cf.dim() >= 2 and cf.shape[-1] == 1 and cf.shape[-2] == n:
             cf = cf.squeeze(-1)
         if Cf.dim() not in (2, 3) or tuple(Cf.shape[-2:]) != (n, n) or cf.dim() not in (1, 2) or cf.shape[-1] != n:
@@ -104,9 +113,9 @@ def tvlqr_box_vjp(F, f, C, c, low, high, states, actions, g_states=None, g_actio
     if unknown:
         raise ValueError(f"cannot give the gradient of {unknown}: not an operand of this call")
     alloc = torch.zeros if B == 0 else torch.empty
-    grads = {k: alloc(ops[k][0].shape, device=dev) for k in want if k != "x0"}
+    grads = {k: alloc(ops[k][0].shape, dtype=dt, device=dev) for k in want if k != "x0"}
     if "x0" in want:
-        grads["x0"] = alloc((B, n), device=dev)
+        grads["x0"] = alloc((B, n), dtype=dt, device=dev)
 
     def out3(k):
         return [_hip.ptr(grads[k]), ops[k][1], ops[k][2]] if k in grads else [None, 0, 0]
@@ -126,19 +135,21 @@ def tvlqr_box_vjp(F, f, C, c, low, high, states, actions, g_states=None, g_actio
         bounds += [_hip.ptr(ops[k][0]), ops[k][1], ops[k][2]]
     ups = []
     for g, ref in ((g_states, states), (g_actions, actions), (g_costs, states[..., 0])):
-        ups.append(None if g is None else _f32(g, dev).reshape(ref.shape).contiguous())
+        ups.append(None if g is None else _cast(g, dev, dt).reshape(ref.shape).contiguous())
     outs = out3("F") + out3("f") + out3("C") + out3("c")
     outs += out2("C_final", ops["C_final"][1] if C_final is not None else 0)
     outs += out2("c_final", ops["c_final"][1] if C_final is not None else 0) + out2("x0", n)
     outs += out3("low") + out3("high")
     mask = torch.zeros((B, T), dtype=torch.int32, device=dev)
     status = torch.zeros((B,), dtype=torch.int32, device=dev)
-    ws_bytes = int(lib.tfmpc_tvlqr_box_vjp_workspace_bytes(B, n, m, T))
-    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
-    rc = lib.tfmpc_tvlqr_box_vjp_f32(B, n, m, T, *model, *bounds, _hip.ptr(states), _hip.ptr(actions),
-                                     *(_hip.ptr(u) for u in ups), *outs, _hip.ptr(mask), _hip.ptr(status), _hip.ptr(ws),
-                                     ws.numel() * 4, _hip.stream())
-    _hip.check(rc, "tfmpc_tvlqr_box_vjp_f32")
+    query, vjp, name = ((lib.tfmpc_tvlqr_box_vjp_workspace_bytes_f64, lib.tfmpc_tvlqr_box_vjp_f64, "tfmpc_tvlqr_box_vjp_f64")
+                        if dt == torch.float64 else
+                        (lib.tfmpc_tvlqr_box_vjp_workspace_bytes, lib.tfmpc_tvlqr_box_vjp_f32, "tfmpc_tvlqr_box_vjp_f32"))
+    ws_bytes = int(query(B, n, m, T))
+    ws = torch.empty((max(ws_bytes, size) + size - 1) // size, dtype=dt, device=dev)
+    rc = vjp(B, n, m, T, *model, *bounds, _hip.ptr(states), _hip.ptr(actions), *(_hip.ptr(u) for u in ups), *outs,
+             _hip.ptr(mask), _hip.ptr(status), _hip.ptr(ws), ws.numel() * size, _hip.stream())
+    _hip.check(rc, name)
     grads["clamped"] = (mask.unsqueeze(-1) >> torch.arange(m, device=dev, dtype=torch.int32)) & 1 != 0
     grads["status"] = status
     return grads

@@ -1,6 +1,6 @@
 """Control-limited time-varying LQR: ``tfmpc_tvlqr_box_solve_f32`` (include/tfmpc_hip.h), the forward
 of :func:`tfmpc.solvers.tvlqr_box_vjp`, and its double-precision twin ``tfmpc_tvlqr_box_solve_f64`` (DESIGN.md §3.18,
-``dtype=torch.float64``: n <= 32, no gradients).
+``dtype=torch.float64``: n <= 32; gradients on request, ``differentiable=True``, through ``tfmpc_tvlqr_box_vjp_f64``, §3.20).
 
 The problem of :class:`tfmpc.solvers.TimeVaryingLQR` under ``low <= u_t <= high``: a convex QP with an exact model,
 solved per instance by control-limited Newton sweeps without regularisation.  Models may vary in time and by instance,
@@ -129,7 +129,7 @@ class TvBoxSolveFunction(torch.autograd.Function):
         F, f, C, c, low, high, Cf, cf = ctx.ops
         want = tuple(k for k, need in zip(GRAD_NAMES, ctx.needs_input_grad[1:]) if need)
         got = tvlqr_box_vjp(F, f, C, c, low, high, states, actions, g_states, g_actions, g_costs, C_final=Cf, c_final=cf,
-                            want=want)
+                            want=want, dtype=ctx.call.dtype)
         info = ctx.call.info
         info.last_grad_status, info.last_clamped = got["status"], got["clamped"]
         shapes = dict(zip(GRAD_NAMES, (F, f, C, c, states[:, 0], low, high, Cf, cf)))
@@ -137,7 +137,7 @@ class TvBoxSolveFunction(torch.autograd.Function):
 
 
 def tvlqr_box_solve(F, f, C, c, x0, low, high, C_final=None, c_final=None, u_init=None, max_iter=None, tol=None,
-                    dtype=None):
+                    dtype=None, differentiable=False):
     """Solve ``min sum_t 1/2 z_t^T C_t z_t + c_t^T z_t + 1/2 x_T^T C_fin x_T + c_fin^T x_T``, ``x_{t+1} = F_t z_t + f_t``,
     ``low_t <= u_t <= high_t`` from ``x0`` and return ``(states, actions, costs)`` -- ``states[(B,)T+1,n,1]``,
     ``actions[(B,)T,m,1]``, ``costs[(B,)T+1,1,1]`` as :func:`tfmpc.solvers.box_lqr_solve` -- with ``.info``
@@ -163,16 +163,19 @@ def tvlqr_box_solve(F, f, C, c, x0, low, high, C_final=None, c_final=None, u_ini
     ``dtype``: ``None`` or ``torch.float32`` is the fp32 kernel; float64 inputs are cast to fp32, silently.
     ``torch.float64`` keeps tensor and numpy operands, bounds, ``x0``, ``u_init`` and the final cost in double, with no
     pass through fp32, runs ``tfmpc_tvlqr_box_solve_f64`` (n <= 32, ``tol`` defaults to 1e-12) and
-    returns float64 tensors; a held control carries the double bound's bits.  Gradients are fp32 only: with
-    ``torch.float64`` an operand that requires grad raises ``NotImplementedError``."""
+    returns float64 tensors; a held control carries the double bound's bits.  Double gradients are opt-in: with
+    ``torch.float64`` an operand that requires grad raises ``NotImplementedError`` unless ``differentiable=True``, which
+    runs the same forward on the detached operands (the same trajectory, bit for bit) and puts the result in the graph
+    with ``tvlqr_box_vjp(dtype=torch.float64)`` as its backward (once differentiable).  With ``dtype``
+    fp32 or ``None`` the flag changes nothing."""
     if dtype not in (None, torch.float32, torch.float64):
         raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype!r}")
     dt = torch.float64 if dtype == torch.float64 else torch.float32
     given = (F, f, C, c, x0, low, high, C_final, c_final)
-    if dt == torch.float64 and wants_grad(*given):
-        raise NotImplementedError("gradients of the control-limited time-varying LQR in double are not served: the box VJP "
-                                  "is fp32 only, call with dtype=torch.float32, or detach the operands, bounds and x0 for a "
-                                  "dtype=torch.float64 solve")
+    if dt == torch.float64 and not differentiable and wants_grad(*given):
+        raise NotImplementedError("gradients of the control-limited time-varying LQR in double are opt-in: pass "
+                                  "differentiable=True for the double box VJP, call with dtype=torch.float32, or detach "
+                                  "the operands, bounds and x0 for a dtype=torch.float64 solve")
     dev = next((t.device for t in given if isinstance(t, torch.Tensor) and t.device.type != "cpu"), _hip.default_device())
     if (C_final is None) != (c_final is None):
         raise ValueError("give both C_final and c_final, or neither")
