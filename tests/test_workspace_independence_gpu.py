@@ -1,6 +1,10 @@
 """No result may depend on what the caller's workspace held before the call.  Every solver entry point takes its scratch
 from the caller (include/tfmpc_hip.h: "Scratch is passed in explicitly"), so the same buffer is reused across calls and
-shapes; each kernel family is run with the workspace pre-filled with zeros, NaN and +inf and must return identical bits.
+shapes.  This file covers the two families whose ``solve_device`` takes a ``workspace``: ``iLQR.solve_device`` (the
+costate, lane, group, LQ-env and navigation kernels) and ``LQR.solve_device``; each is run with the workspace pre-filled
+with zeros, NaN and +inf and must return identical bits.  The time-varying, time-parallel, control-limited and
+steady-state solves and every gradient family, whose front ends allocate workspace, outputs and gradient buffers
+themselves, are held to the same rule by tests/test_stale_memory_gpu.py (through tests/stale_memory.py).
 (Found with tools/probes/fuzz_costate.py: with several instances per matrix-core column the empty sub-columns of the last
 wave read trajectory slots nobody had written, and a stale NaN reached the live rows through 0 x NaN.)"""
 
