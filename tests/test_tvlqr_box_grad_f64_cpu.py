@@ -30,6 +30,12 @@ from tfmpc import solvers  # noqa: E402
 LD = np.longdouble
 EXPORTS = ("tfmpc_tvlqr_box_vjp_workspace_bytes_f64", "tfmpc_tvlqr_box_vjp_kernel_name_f64", "tfmpc_tvlqr_box_vjp_f64")
 SHAPES = [(5, 3, 6), (3, 5, 6)]
+# tvlqr_vjp_f64.hip's kernels by their mangled stems (as in tests/test_tvlqr_grad_f64_cpu.py): the folds, the status OR,
+# the costates <LOOP, BOX>, the model's batch sums and the bounds' two
+F64_VJP_KERNELS = ("15vjp_fold_kernelE", "19box_fold_f64_kernelE", "20box_status_or_kernelE", "18vjp_costate_kernelILb0ELb0EE",
+                   "18vjp_costate_kernelILb1ELb0EE", "18vjp_costate_kernelILb0ELb1EE", "18vjp_costate_kernelILb1ELb1EE",
+                   "16vjp_reduce_finalIdE", "16vjp_reduce_stepsIdE", "23vjp_reduce_steps_mfma16IdE", "23vjp_reduce_steps_stage2IdE",
+                   "17box_reduce_boundsIdE", "16box_reduce_finalIdE")
 
 
 def _exact_case(n, m, T, B=4):
@@ -364,12 +370,15 @@ def _assembly(source):
 
 @pytest.mark.skipif(check_ring_waits.hipcc_path() is None, reason="needs the device compiler (hipcc) to produce the assembly")
 def test_the_new_kernels_use_no_scratch_and_fit_the_register_file():
-    found, bodies = _assembly("tvlqr_box_vjp_f64.hip")
-    own = [row for row in found if "box_" in row[0]]
-    assert len(own) == 6, found          # fold, status, costates x {per step, per instance}, the bounds' two sums
+    found, bodies = _assembly("tvlqr_vjp_f64.hip")
+    assert len(found) == len(F64_VJP_KERNELS), found
+    for stem in F64_VJP_KERNELS:          # exactly this set: the file holds the plain and the control-limited VJP
+        assert sum(stem in name for name, *_ in found) == 1, (stem, found)
+    assert sum("vjp_" in name for name, *_ in found) == 9 and sum("box_" in name for name, *_ in found) == 4, found
     for name, private, vgprs, spills in found:
         assert int(private) == 0 and int(spills) == 0 and int(vgprs) <= 256, (name, private, vgprs, spills)
         assert "v_mfma_f32" not in bodies[name], name
+        assert ("v_mfma_f64_16x16x4" in bodies[name]) == ("mfma16" in name), name
     found, bodies = _assembly("tvlqr_f64.hip")
     masked = [row for row in found if "tvlqr_masked_f64_sweep" in row[0]]
     assert len(masked) == 4, found       # {wave16, wave32} x {solve, backward only}

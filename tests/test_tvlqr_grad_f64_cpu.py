@@ -27,6 +27,12 @@ LD = np.longdouble
 EXPORTS = ("tfmpc_tvlqr_vjp_workspace_bytes_f64", "tfmpc_tvlqr_vjp_f64")
 LOSSES = ("states", "actions", "costs", "mixed")
 SCALED = [(3, 2, 1), (4, 3, 2), (5, 2, 9), (16, 8, 8)]
+# tvlqr_vjp_f64.hip's kernels by their mangled stems: the folds, the status OR, the costates <LOOP, BOX>, the model's batch
+# sums (final records, per step scalar and matrix-core, stage 2) and the bounds' two
+F64_VJP_KERNELS = ("15vjp_fold_kernelE", "19box_fold_f64_kernelE", "20box_status_or_kernelE", "18vjp_costate_kernelILb0ELb0EE",
+                   "18vjp_costate_kernelILb1ELb0EE", "18vjp_costate_kernelILb0ELb1EE", "18vjp_costate_kernelILb1ELb1EE",
+                   "16vjp_reduce_finalIdE", "16vjp_reduce_stepsIdE", "23vjp_reduce_steps_mfma16IdE", "23vjp_reduce_steps_stage2IdE",
+                   "17box_reduce_boundsIdE", "16box_reduce_finalIdE")
 
 
 def _problem(n, m, T, B, final, seed=0, loss="mixed", unscaled=False):
@@ -168,15 +174,17 @@ def test_the_f64_vjp_kernels_use_no_scratch_and_the_f64_matrix_cores():
         subprocess.run([check_ring_waits.hipcc_path(), *check_ring_waits.FLAGS, "--cuda-device-only", "-S", path, "-o", out], check=True,
                        capture_output=True)
         text = open(out).read()
-    found = re.findall(r"\.name:\s+(\S*vjp_\S*)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
+    found = re.findall(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
                        r"\s+\.vgpr_spill_count:\s+(\d+)", text)
-    # fold, costates per (b, t) and per instance, final-record sums, per-step sums (scalar, matrix-core), stage 2
-    assert len(found) == 7, found
-    assert len(re.findall(r"^\s*\.amdhsa_kernel\s", text, flags=re.M)) == 7
+    assert len(re.findall(r"^\s*\.amdhsa_kernel\s", text, flags=re.M)) == len(found) == len(F64_VJP_KERNELS), found
+    for stem in F64_VJP_KERNELS:          # exactly this set: the file holds the plain and the control-limited VJP
+        assert sum(stem in name for name, *_ in found) == 1, (stem, found)
+    assert sum("vjp_" in name for name, *_ in found) == 9 and sum("box_" in name for name, *_ in found) == 4, found
     for name, private, vgprs, spills in found:
         assert int(private) == 0 and int(spills) == 0 and int(vgprs) <= 256, (name, private, vgprs, spills)
         body = re.search(r"\n" + re.escape(name) + r":.*?\n(.*?)\n\s*\.amdhsa_kernel\s+" + re.escape(name), text, flags=re.S)
         assert body, name
+        assert "v_mfma_f32" not in body.group(1), name
         assert ("v_mfma_f64_16x16x4" in body.group(1)) == ("mfma16" in name), name
 
 

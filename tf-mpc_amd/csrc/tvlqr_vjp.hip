@@ -23,7 +23,9 @@
 // (b, t) and zeroes the held entries of c~; the adjoint solve is the masked sweep (tvlqr_solve_masked_f32: the mask is
 // applied as the model is loaded, no masked copy exists); box_sweep_kernel runs the costate sweep on the UNMASKED model
 // and emits r_t[n + i] = (C_t dz_t + g_t + F_t^T dlam_{t+1})[n + i] of every held control into dlow or dhigh;
-// box_reduce_bounds sums them over the batch in a fixed order.
+// box_shared_sums (tvlqr_vjp_common.h, shared with the double VJP) sums them over the batch in a fixed order.
+// One vjp_impl stands behind both entries; the argument checks and the fill of VjpArgs that do not depend on the precision
+// are tvlqr_vjp_common.h's (vjp_check_call, vjp_fill_base), shared with tvlqr_vjp_f64.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -197,43 +199,6 @@ __global__ void __launch_bounds__(kSweepThreads) box_sweep_kernel(VjpArgs a, boo
     sweep_body<true>(a, store_factors, &bx);
 }
 
-// Bound gradients shared by the batch: partial[(chunk * T + t) * m + e] = sum over the chunk's instances of R[b][t][e],
-// eight interleaved sub-sums per element combined in a fixed order (m <= 32); box_reduce_final sums the chunks.
-__global__ void __launch_bounds__(kRedThreads) box_reduce_bounds(const float *R, int B, int T, int m, float *partial)
-{
-    __shared__ float sub[kRedThreads];
-    const int chunk = blockIdx.x, t = blockIdx.y, e = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const int b0 = chunk * kChunk, b1 = min(B, b0 + kChunk);
-    float s = 0.0f;
-    if (e < m)
-        for (int b = b0 + g; b < b1; b += kRedThreads / 32) s += R[((size_t)b * T + t) * m + e];
-    sub[threadIdx.x] = s;
-    __syncthreads();
-    if (g == 0 && e < m) {
-        for (int k = 1; k < kRedThreads / 32; ++k) s += sub[32 * k + e];
-        partial[((size_t)chunk * T + t) * m + e] = s;
-    }
-}
-
-// out[slot * st + e] = sum over the chunks (and, untimed, the steps) of partial[(chunk * T + t) * m + e]: one block per
-// (element, slot), 256 strided sub-sums and an LDS tree -- a fixed order, so the same call gives the same bits.
-__global__ void __launch_bounds__(kRedThreads) box_reduce_final(const float *partial, int chunks, int T, int m, bool timed,
-                                                                float *out, long st)
-{
-    __shared__ float sub[kRedThreads];
-    const int e = blockIdx.x, slot = blockIdx.y, tid = threadIdx.x;
-    const int t0 = timed ? slot : 0, nt = timed ? 1 : T, total = chunks * nt;
-    float s = 0.0f;
-    for (int q = tid; q < total; q += kRedThreads) s += partial[((size_t)(q / nt) * T + t0 + q % nt) * m + e];
-    sub[tid] = s;
-    __syncthreads();
-    for (int w = kRedThreads / 2; w > 0; w >>= 1) {
-        if (tid < w) sub[tid] += sub[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) out[(size_t)slot * st + e] = sub[0];
-}
-
 // ---- launch helpers --------------------------------------------------------------------------------------------------
 size_t fold_smem_bytes(int n, int m) { return fold_smem_elems(n, m) * sizeof(float); }
 
@@ -275,141 +240,29 @@ BoxLayout box_layout(int B, int n, int m, int T)
     return L;
 }
 
-struct BoxCall {
-    const float *low, *high;
-    long slo_b, slo_t, shi_b, shi_t;
-    float *dlow, *dhigh;
-    long sdlo_b, sdlo_t, sdhi_b, sdhi_t;
-    uint32_t *clamp_mask;
-};
-
-int vjp_impl(int B, int n, int m, int T,
-             const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
-             const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t,
-             const float *Cfin, long sCfin_b, const float *cfin, long scfin_b,
-             const float *states, const float *actions,
-             const float *g_states, const float *g_actions, const float *g_costs,
-             float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t,
-             float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
-             float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b,
-             int32_t *status, void *workspace, size_t workspace_bytes, void *stream, const BoxCall *box);
-
-}  // namespace
-
-extern "C" {
-
-size_t tfmpc_tvlqr_vjp_workspace_bytes(int B, int n, int m, int T)
+// Both entries; box: the control-limited one's extra arguments.  The checks and the fill of VjpArgs that do not depend
+// on the precision are tvlqr_vjp_common.h's.
+int vjp_impl(const VjpCall<float> &c, const BoxCall<float> *box)
 {
-    if (B <= 0 || n <= 0 || m <= 0 || T <= 0) return 0;
-    return layout(B, n, m, T).total * sizeof(float);
-}
-
-#define TFMPC_VJP_PARAMS_HEAD                                                                                      \
-    int B, int n, int m, int T, const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,          \
-        const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t, const float *Cfin, long sCfin_b, \
-        const float *cfin, long scfin_b
-#define TFMPC_VJP_PARAMS_TAIL                                                                                      \
-    const float *states, const float *actions, const float *g_states, const float *g_actions, const float *g_costs, \
-        float *dF, long sdF_b, long sdF_t, float *df, long sdf_b, long sdf_t, float *dC, long sdC_b, long sdC_t,    \
-        float *dc, long sdc_b, long sdc_t, float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0,    \
-        long sdx0_b
-#define TFMPC_VJP_HEAD B, n, m, T, F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b
-#define TFMPC_VJP_TAIL                                                                                             \
-    states, actions, g_states, g_actions, g_costs, dF, sdF_b, sdF_t, df, sdf_b, sdf_t, dC, sdC_b, sdC_t, dc, sdc_b, \
-        sdc_t, dCfin, sdCfin_b, dcfin, sdcfin_b, dx0, sdx0_b
-
-int tfmpc_tvlqr_vjp_f32(TFMPC_VJP_PARAMS_HEAD, TFMPC_VJP_PARAMS_TAIL, int32_t *status, void *workspace,
-                        size_t workspace_bytes, void *stream)
-{
-    return vjp_impl(TFMPC_VJP_HEAD, TFMPC_VJP_TAIL, status, workspace, workspace_bytes, stream, nullptr);
-}
-
-size_t tfmpc_tvlqr_box_vjp_workspace_bytes(int B, int n, int m, int T)
-{
-    if (B <= 0 || n <= 0 || m <= 0 || T <= 0) return 0;
-    return box_layout(B, n, m, T).total * sizeof(float);
-}
-
-const char *tfmpc_tvlqr_box_vjp_kernel_name(int n, int m, int T)
-{
-    (void)T;
-    if (n <= 0 || m <= 0) return "invalid";
-    if (tvlqr_mfma_supported(n, m)) return (n == 16 && m == 8) ? "tv_masked_16x8" : "tv_masked_16x8 (zero-padded)";
-    if (m > 32 || tvlqr_generic_smem_bytes(n, m) > kMaxLdsBytes || sweep_smem_bytes(n, m) > kMaxLdsBytes) return "unsupported";
-    return "tv_masked_generic_wave";
-}
-
-int tfmpc_tvlqr_box_vjp_f32(TFMPC_VJP_PARAMS_HEAD, const float *low, long slow_b, long slow_t, const float *high,
-                            long shigh_b, long shigh_t, TFMPC_VJP_PARAMS_TAIL, float *dlow, long sdlow_b, long sdlow_t,
-                            float *dhigh, long sdhigh_b, long sdhigh_t, uint32_t *clamp_mask, int32_t *status,
-                            void *workspace, size_t workspace_bytes, void *stream)
-{
-    const BoxCall box{low, high, slow_b, slow_t, shigh_b, shigh_t, dlow, dhigh, sdlow_b, sdlow_t, sdhigh_b, sdhigh_t,
-                      clamp_mask};
-    return vjp_impl(TFMPC_VJP_HEAD, TFMPC_VJP_TAIL, status, workspace, workspace_bytes, stream, &box);
-}
-
-}  // extern "C"
-
-namespace {
-
-int vjp_impl(TFMPC_VJP_PARAMS_HEAD, TFMPC_VJP_PARAMS_TAIL, int32_t *status, void *workspace, size_t workspace_bytes,
-             void *stream, const BoxCall *box)
-{
+    const int B = c.B, n = c.n, m = c.m, T = c.T, d = n + m;
     if (B < 0 || n <= 0 || m <= 0 || T <= 0) return TFMPC_ERR_ARG;
     if (!tvlqr_mfma_supported(n, m) && tvlqr_generic_smem_bytes(n, m) > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
     if (B == 0) return TFMPC_OK;
-    if (!F || !f || !C || !c || !states || !actions || !status) return TFMPC_ERR_ARG;
-    if (!Cfin != !cfin) return TFMPC_ERR_ARG;
-    if (!Cfin && (dCfin || dcfin)) return TFMPC_ERR_ARG;           // the default final cost's gradient is in dC, dc
-    if (T > 65535) return TFMPC_ERR_UNSUPPORTED;                   // per-step reduction slots are one grid axis
-    if ((size_t)B * (T + 1) > 0x7fffffffu) return TFMPC_ERR_UNSUPPORTED;   // fold: one block per (b, t)
-    if (sweep_smem_bytes(n, m) > kMaxLdsBytes || fold_smem_bytes(n, m) > kMaxLdsBytes) return TFMPC_ERR_UNSUPPORTED;
-    if (box) {
-        if (m > 32) return TFMPC_ERR_UNSUPPORTED;                  // one held-set word per step
-        if (!box->low || !box->high) return TFMPC_ERR_ARG;
-        for (long s : {box->slo_b, box->slo_t, box->shi_b, box->shi_t, box->sdlo_b, box->sdlo_t, box->sdhi_b, box->sdhi_t})
-            if (s < 0) return TFMPC_ERR_ARG;
-    }
-    for (long s : {sF_b, sF_t, sf_b, sf_t, sC_b, sC_t, sc_b, sc_t, sCfin_b, scfin_b, sdF_b, sdF_t, sdf_b, sdf_t,
-                   sdC_b, sdC_t, sdc_b, sdc_t, sdCfin_b, sdcfin_b, sdx0_b})
-        if (s < 0) return TFMPC_ERR_ARG;
+    const bool fits = sweep_smem_bytes(n, m) <= kMaxLdsBytes && fold_smem_bytes(n, m) <= kMaxLdsBytes &&
+                      !(box && m > 32);                            // one held-set word per step
+    if (const int rc = vjp_check_call(c, box, fits); rc != TFMPC_OK) return rc;
     const Layout L = layout(B, n, m, T);
     const BoxLayout XL = box ? box_layout(B, n, m, T) : BoxLayout{};
-    if (!workspace || workspace_bytes < (box ? XL.total : L.total) * sizeof(float)) return TFMPC_ERR_WORKSPACE;
-    const int d = n + m;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *w = static_cast<float *>(workspace);
+    if (!c.workspace || c.workspace_bytes < (box ? XL.total : L.total) * sizeof(float)) return TFMPC_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    float *w = static_cast<float *>(c.workspace);
 
     VjpArgs a{};
-    a.B = B; a.n = n; a.m = m; a.T = T;
-    a.F = F; a.sF_b = sF_b; a.sF_t = sF_t;
-    a.C = C; a.sC_b = sC_b; a.sC_t = sC_t;
-    a.c = c; a.sc_b = sc_b; a.sc_t = sc_t;
-    a.dflt = Cfin == nullptr;
-    a.states = states; a.actions = actions; a.gx = g_states; a.gu = g_actions; a.gc = g_costs;
-    a.dS = w + L.dS; a.dA = w + L.dA; a.ct = w + L.ct; a.cT = w + L.cT;
-    a.status = status; a.poison_mask = kPoison;
+    vjp_fill_base(a, c, w, L);
+    a.poison_mask = kPoison;
     a.P = w + L.P; a.a0 = w + L.Pf; a.sa0_b = n;
-    if (a.dflt) {                    // the fold's copy of C_{T-1}[:n,:n]; c_{T-1}[:n], contiguous in c
-        a.Cf = w + L.Cfe; a.sCf_b = sC_b ? (long)n * n : 0;
-        a.cf = c + (size_t)(T - 1) * sc_t; a.scf_b = sc_b;
-    } else {
-        a.Cf = Cfin; a.sCf_b = sCfin_b;
-        a.cf = cfin; a.scf_b = scfin_b;
-    }
-    Out outs[kKinds] = {{dF, sdF_b, sdF_t}, {df, sdf_b, sdf_t}, {dC, sdC_b, sdC_t}, {dc, sdc_b, sdc_t},
-                        {dCfin, sdCfin_b, 0}, {dcfin, sdcfin_b, 0}, {dx0, sdx0_b, 0}};
-    for (int k = 0; k < kKinds; ++k) a.o[k] = outs[k];
     BoxArgs bx{};
-    if (box) {
-        bx.low = box->low; bx.slo_b = box->slo_b; bx.slo_t = box->slo_t;
-        bx.high = box->high; bx.shi_b = box->shi_b; bx.shi_t = box->shi_t;
-        bx.mask = reinterpret_cast<uint32_t *>(w + XL.mask); bx.mask_out = box->clamp_mask;
-        bx.Rlo = w + XL.Rlo; bx.Rhi = w + XL.Rhi;
-        bx.olo = Out{box->dlow, box->sdlo_b, box->sdlo_t};
-        bx.ohi = Out{box->dhigh, box->sdhi_b, box->sdhi_t};
-    }
+    if (box) box_fill(bx, *box, reinterpret_cast<uint32_t *>(w + XL.mask), w + XL.Rlo, w + XL.Rhi);
 
     // 1. fold
     {
@@ -428,17 +281,17 @@ int vjp_impl(TFMPC_VJP_PARAMS_HEAD, TFMPC_VJP_PARAMS_TAIL, int32_t *status, void
     {
         int rc;
         if (box)                     // the held controls taken out of the model as it is loaded
-            rc = tvlqr_solve_masked_f32(B, n, m, T, F, sF_b, sF_t, w + L.zer, 0, 0, C, sC_b, sC_t, w + L.ct, (long)T * d, d,
-                                        a.Cf, a.sCf_b, w + L.cT, n, w + L.zer, w + L.dS, w + L.dA, w + L.dcost, status,
-                                        bx.mask, w + L.solve, L.solve_bytes, stream);
+            rc = tvlqr_solve_masked_f32(B, n, m, T, c.F, c.sF_b, c.sF_t, w + L.zer, 0, 0, c.C, c.sC_b, c.sC_t, w + L.ct, (long)T * d, d,
+                                        a.Cf, a.sCf_b, w + L.cT, n, w + L.zer, w + L.dS, w + L.dA, w + L.dcost, c.status,
+                                        bx.mask, w + L.solve, L.solve_bytes, c.stream);
         else
-            rc = tfmpc_tvlqr_solve_f32(B, n, m, T, F, sF_b, sF_t, w + L.zer, 0, 0, C, sC_b, sC_t, w + L.ct, (long)T * d, d,
+            rc = tfmpc_tvlqr_solve_f32(B, n, m, T, c.F, c.sF_b, c.sF_t, w + L.zer, 0, 0, c.C, c.sC_b, c.sC_t, w + L.ct, (long)T * d, d,
                                        a.Cf, a.sCf_b, w + L.cT, n, w + L.zer, w + L.dS, w + L.dA, w + L.dcost, nullptr,
-                                       nullptr, nullptr, nullptr, nullptr, status, w + L.solve, L.solve_bytes, stream);
+                                       nullptr, nullptr, nullptr, nullptr, c.status, w + L.solve, L.solve_bytes, c.stream);
         if (rc != TFMPC_OK) return rc;
     }
     // 3. sweep
-    const bool reduce_F = (dF && !sdF_b) || (df && !sdf_b);
+    const bool reduce_F = (c.dF && !c.sdF_b) || (c.df && !c.sdf_b);
     {
         const size_t smem = sweep_smem_bytes(n, m);
         if (box) {
@@ -450,24 +303,66 @@ int vjp_impl(TFMPC_VJP_PARAMS_HEAD, TFMPC_VJP_PARAMS_TAIL, int32_t *status, void
         }
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
     }
-    // 4. shared gradients
+    // 4. shared gradients: the model's, then the bounds' from the sweep's records
     float *partial = w + L.partial;
     if (const int rc = vjp_shared_sums<float>(a, partial, s); rc != TFMPC_OK) return rc;
-    if (box) {                       // bound gradients shared by the batch: the sweep's records, chunks, then steps
-        const int chunks = (B + kChunk - 1) / kChunk;
-        const Out bo[2] = {bx.olo, bx.ohi};
-        const float *rec[2] = {bx.Rlo, bx.Rhi};
-        for (int k = 0; k < 2; ++k) {
-            if (!bo[k].p || bo[k].sb) continue;
-            hipLaunchKernelGGL(box_reduce_bounds, dim3(chunks, T), dim3(kRedThreads), 0, s, rec[k], B, T, m, partial);
-            if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-            const bool timed = bo[k].st != 0;
-            hipLaunchKernelGGL(box_reduce_final, dim3(m, timed ? T : 1), dim3(kRedThreads), 0, s, partial, chunks, T, m, timed,
-                               bo[k].p, bo[k].st);
-            if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-        }
-    }
-    return TFMPC_OK;
+    return box ? box_shared_sums<float>(bx, B, T, m, partial, s) : TFMPC_OK;
 }
 
 }  // namespace
+
+extern "C" {
+
+size_t tfmpc_tvlqr_vjp_workspace_bytes(int B, int n, int m, int T)
+{
+    if (B <= 0 || n <= 0 || m <= 0 || T <= 0) return 0;
+    return layout(B, n, m, T).total * sizeof(float);
+}
+
+int tfmpc_tvlqr_vjp_f32(int B, int n, int m, int T, const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                        const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t, const float *Cfin,
+                        long sCfin_b, const float *cfin, long scfin_b, const float *states, const float *actions,
+                        const float *g_states, const float *g_actions, const float *g_costs, float *dF, long sdF_b, long sdF_t,
+                        float *df, long sdf_b, long sdf_t, float *dC, long sdC_b, long sdC_t, float *dc, long sdc_b, long sdc_t,
+                        float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0, long sdx0_b, int32_t *status,
+                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    return vjp_impl({B, n, m, T, F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b, states,
+                     actions, g_states, g_actions, g_costs, dF, sdF_b, sdF_t, df, sdf_b, sdf_t, dC, sdC_b, sdC_t, dc, sdc_b, sdc_t,
+                     dCfin, sdCfin_b, dcfin, sdcfin_b, dx0, sdx0_b, status, workspace, workspace_bytes, stream},
+                    nullptr);
+}
+
+size_t tfmpc_tvlqr_box_vjp_workspace_bytes(int B, int n, int m, int T)
+{
+    if (B <= 0 || n <= 0 || m <= 0 || T <= 0) return 0;
+    return box_layout(B, n, m, T).total * sizeof(float);
+}
+
+const char *tfmpc_tvlqr_box_vjp_kernel_name(int n, int m, int T)
+{
+    (void)T;
+    if (n <= 0 || m <= 0) return "invalid";
+    if (tvlqr_mfma_supported(n, m)) return (n == 16 && m == 8) ? "tv_masked_16x8" : "tv_masked_16x8 (zero-padded)";
+    if (m > 32 || tvlqr_generic_smem_bytes(n, m) > kMaxLdsBytes || sweep_smem_bytes(n, m) > kMaxLdsBytes) return "unsupported";
+    return "tv_masked_generic_wave";
+}
+
+int tfmpc_tvlqr_box_vjp_f32(int B, int n, int m, int T, const float *F, long sF_b, long sF_t, const float *f, long sf_b, long sf_t,
+                            const float *C, long sC_b, long sC_t, const float *c, long sc_b, long sc_t, const float *Cfin,
+                            long sCfin_b, const float *cfin, long scfin_b, const float *low, long slow_b, long slow_t,
+                            const float *high, long shigh_b, long shigh_t, const float *states, const float *actions,
+                            const float *g_states, const float *g_actions, const float *g_costs, float *dF, long sdF_b,
+                            long sdF_t, float *df, long sdf_b, long sdf_t, float *dC, long sdC_b, long sdC_t, float *dc,
+                            long sdc_b, long sdc_t, float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b, float *dx0,
+                            long sdx0_b, float *dlow, long sdlow_b, long sdlow_t, float *dhigh, long sdhigh_b, long sdhigh_t,
+                            uint32_t *clamp_mask, int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const BoxCall<float> box{low, slow_b, slow_t, high, shigh_b, shigh_t, dlow, sdlow_b, sdlow_t, dhigh, sdhigh_b, sdhigh_t, clamp_mask};
+    return vjp_impl({B, n, m, T, F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, Cfin, sCfin_b, cfin, scfin_b, states,
+                     actions, g_states, g_actions, g_costs, dF, sdF_b, sdF_t, df, sdf_b, sdf_t, dC, sdC_b, sdC_t, dc, sdc_b, sdc_t,
+                     dCfin, sdCfin_b, dcfin, sdcfin_b, dx0, sdx0_b, status, workspace, workspace_bytes, stream},
+                    &box);
+}
+
+}  // extern "C"

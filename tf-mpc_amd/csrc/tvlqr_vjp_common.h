@@ -1,19 +1,22 @@
 // tvlqr_vjp_common.h -- what the gradients of the fp32 and of the double-precision TV-LQR solve share (tvlqr_vjp.hip,
-// tvlqr_vjp_f64.hip), templated on the scalar S: the fold, the batch reductions and the host code
-// that enqueues them.  The two files differ in the costates (open-loop recursion / value function), which stay there.
+// tvlqr_vjp_f64.hip), templated on the scalar S: the fold, the batch reductions (the
+// model's and the bounds') with the host code that enqueues them, and the argument contract of the four C entries --
+// their arguments as one aggregate, the checks that do not depend on a precision's kernels, the fill of VjpBase<S>.
+// The two files differ in the costates (open-loop recursion / value function), which stay there.
 //
 // Batch reductions: gradients with batch stride 0.  dF, df, dC, dc: ONE pass per (chunk of instances, step) emits all
 // four partial sums -- GEMMs over instances on the 16x16x4 matrix-core instruction of S for n <= 16, d <= 32
 // (vjp_reduce_steps_mfma16), LDS-tiled scalar sums otherwise (vjp_reduce_steps) -- then a fixed-order sum over chunks per
 // output (vjp_reduce_steps_stage2).  dCfin, dcfin, dx0: one record per instance, vjp_reduce_final, then the chunks in
-// order (vjp_reduce_steps_stage2 with T = 1).  No atomics: the same call gives the same bits.
+// order (vjp_reduce_steps_stage2 with T = 1).  dlow, dhigh: box_reduce_bounds per (chunk, step), box_reduce_final over
+// chunks and steps.  No atomics: the same call gives the same bits.
 //
 // Workspace in elements of S, every array rounded up to 64: ct [B][T][d], cT [B][n], Cfe [B][n][n], zer [B][n],
 // dS [B][T + 1][n], dA [B][T][m], dcost [B][T + 1] (VjpPrefix); the adjoint solve's own workspace; then
 //   fp32:  P [B][T][2n], Pf [B][n], partial
 //   fp64:  V [B][T][n][n], vt [B][T][n], P [B][T][2n], partial
 // with partial [chunks][T][E], E = n d + n + d d + d (>= chunks n n of the final-cost sums); the control-limited VJP
-// appends mask [B][T], Rlo and Rhi [B][T][m] (fp32; the double one, tvlqr_box_vjp_f64.hip, states its own tail there).
+// appends mask [B][T], Rlo and Rhi [B][T][m] (fp32; the double one states its longer tail at tvlqr_vjp_f64.hip's BoxLayout).
 //
 // The build is -ffp-contract=off: every fused multiply-add is a written fma().
 #pragma once
@@ -64,8 +67,8 @@ struct VjpBase {
 };
 
 // The control-limited VJP's extra operands.  fp32: Rlo doubles as the fold's record of the unmasked g_u (read by the
-// sweep before it overwrites the entry with the bound's gradient); the double VJP (tvlqr_box_vjp_f64.hip) hands the fold
-// a record of its own in Rlo's place.
+// sweep before it overwrites the entry with the bound's gradient); the double VJP (tvlqr_vjp_f64.hip's BoxArgs) hands
+// the fold a record of its own in Rlo's place.
 template <class S>
 struct BoxArgsT {
     const S *low, *high;
@@ -73,6 +76,40 @@ struct BoxArgsT {
     uint32_t *mask, *mask_out;       // [B][T]: workspace, caller's (optional)
     S *Rlo, *Rhi;                    // [B][T][m]
     OutT<S> olo, ohi;
+};
+
+// The arguments of a C entry (include/tfmpc_hip.h), in the order the entries take them: what all four VJP entries
+// share, and what the two control-limited ones add.
+template <class S>
+struct VjpCall {
+    int B, n, m, T;
+    const S *F; long sF_b, sF_t;
+    const S *f; long sf_b, sf_t;
+    const S *C; long sC_b, sC_t;
+    const S *c; long sc_b, sc_t;
+    const S *Cfin; long sCfin_b;
+    const S *cfin; long scfin_b;
+    const S *states, *actions, *g_states, *g_actions, *g_costs;
+    S *dF; long sdF_b, sdF_t;
+    S *df; long sdf_b, sdf_t;
+    S *dC; long sdC_b, sdC_t;
+    S *dc; long sdc_b, sdc_t;
+    S *dCfin; long sdCfin_b;
+    S *dcfin; long sdcfin_b;
+    S *dx0; long sdx0_b;
+    int32_t *status;
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+};
+
+template <class S>
+struct BoxCall {
+    const S *low; long slo_b, slo_t;
+    const S *high; long shi_b, shi_t;
+    S *dlow; long sdlo_b, sdlo_t;
+    S *dhigh; long sdhi_b, sdhi_t;
+    uint32_t *clamp_mask;
 };
 
 __device__ inline bool same_bits(float x, float y) { return __float_as_uint(x) == __float_as_uint(y); }
@@ -234,6 +271,44 @@ __global__ void __launch_bounds__(kRedThreads) vjp_reduce_final(VjpBase<S> a, in
             if (e < nE) partial[(size_t)chunk * nE + e] = acc[q];
         }
     }
+}
+
+// Bound gradients shared by the batch (the control-limited VJPs): partial[(chunk * T + t) * m + e] = sum over the chunk's
+// instances of R[b][t][e], eight interleaved sub-sums per element combined in a fixed order (m <= 32).
+template <class S>
+__global__ void __launch_bounds__(kRedThreads) box_reduce_bounds(const S *R, int B, int T, int m, S *partial)
+{
+    __shared__ S sub[kRedThreads];
+    const int chunk = blockIdx.x, t = blockIdx.y, e = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int b0 = chunk * kChunk, b1 = min(B, b0 + kChunk);
+    S s = 0;
+    if (e < m)
+        for (int b = b0 + g; b < b1; b += kRedThreads / 32) s += R[((size_t)b * T + t) * m + e];
+    sub[threadIdx.x] = s;
+    __syncthreads();
+    if (g == 0 && e < m) {
+        for (int k = 1; k < kRedThreads / 32; ++k) s += sub[32 * k + e];
+        partial[((size_t)chunk * T + t) * m + e] = s;
+    }
+}
+
+// out[slot * st + e] = sum over the chunks (and, untimed, the steps) of partial[(chunk * T + t) * m + e]: one block per
+// (element, slot), 256 strided sub-sums and an LDS tree -- a fixed order, so the same call gives the same bits.
+template <class S>
+__global__ void __launch_bounds__(kRedThreads) box_reduce_final(const S *partial, int chunks, int T, int m, bool timed, S *out, long st)
+{
+    __shared__ S sub[kRedThreads];
+    const int e = blockIdx.x, slot = blockIdx.y, tid = threadIdx.x;
+    const int t0 = timed ? slot : 0, nt = timed ? 1 : T, total = chunks * nt;
+    S s = 0;
+    for (int q = tid; q < total; q += kRedThreads) s += partial[((size_t)(q / nt) * T + t0 + q % nt) * m + e];
+    sub[tid] = s;
+    __syncthreads();
+    for (int w = kRedThreads / 2; w > 0; w >>= 1) {
+        if (tid < w) sub[tid] += sub[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[(size_t)slot * st + e] = sub[0];
 }
 
 // Fused per-step reductions: ONE pass over the records emits every requested batch-shared per-step gradient (dF, df,
@@ -448,6 +523,25 @@ int vjp_shared_sums(const VjpBase<S> &a, S *partial, hipStream_t s)
     return TFMPC_OK;
 }
 
+// Enqueues the sums of dlow / dhigh where the batch shares them: the records per (b, t), chunks, then steps.
+template <class S>
+int box_shared_sums(const BoxArgsT<S> &bx, int B, int T, int m, S *partial, hipStream_t s)
+{
+    const int chunks = (B + kChunk - 1) / kChunk;
+    const OutT<S> bo[2] = {bx.olo, bx.ohi};
+    const S *rec[2] = {bx.Rlo, bx.Rhi};
+    for (int k = 0; k < 2; ++k) {
+        if (!bo[k].p || bo[k].sb) continue;
+        hipLaunchKernelGGL(box_reduce_bounds<S>, dim3(chunks, T), dim3(kRedThreads), 0, s, rec[k], B, T, m, partial);
+        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
+        const bool timed = bo[k].st != 0;
+        hipLaunchKernelGGL(box_reduce_final<S>, dim3(m, timed ? T : 1), dim3(kRedThreads), 0, s, partial, chunks, T, m, timed,
+                           bo[k].p, bo[k].st);
+        if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
+    }
+    return TFMPC_OK;
+}
+
 // ---- workspace -------------------------------------------------------------------------------------------------------
 inline size_t fold_smem_elems(int n, int m) { const size_t d = n + m; return d * (d + 1) + d; }
 
@@ -474,6 +568,67 @@ inline size_t vjp_prefix(VjpPrefix &L, int B, int n, int m, int T)
 inline size_t vjp_partial_elems(int B, int n, int m, int T)
 {
     return up64(((size_t)B + kChunk - 1) / kChunk * T * (size_t)steps_E(n, n + m));
+}
+
+// ---- the argument contract of the four entries -------------------------------------------------------------------------
+// The checks that follow an entry's own shape test and its B == 0 return, in the order every entry has always made them.
+// fits: the precision's own refusals (LDS sizes, the held-set word), which come after the grid limits and before the
+// bounds' operands.
+template <class S>
+int vjp_check_call(const VjpCall<S> &c, const BoxCall<S> *box, bool fits)
+{
+    if (!c.F || !c.f || !c.C || !c.c || !c.states || !c.actions || !c.status) return TFMPC_ERR_ARG;
+    if (!c.Cfin != !c.cfin) return TFMPC_ERR_ARG;
+    if (!c.Cfin && (c.dCfin || c.dcfin)) return TFMPC_ERR_ARG;     // the default final cost's gradient is in dC, dc
+    if (c.T > 65535) return TFMPC_ERR_UNSUPPORTED;                 // per-step reduction slots are one grid axis
+    if ((size_t)c.B * (c.T + 1) > 0x7fffffffu) return TFMPC_ERR_UNSUPPORTED;   // fold (double: costates too): one block per (b, t)
+    if (!fits) return TFMPC_ERR_UNSUPPORTED;
+    if (box) {
+        if (!box->low || !box->high) return TFMPC_ERR_ARG;
+        for (long s : {box->slo_b, box->slo_t, box->shi_b, box->shi_t, box->sdlo_b, box->sdlo_t, box->sdhi_b, box->sdhi_t})
+            if (s < 0) return TFMPC_ERR_ARG;
+    }
+    for (long s : {c.sF_b, c.sF_t, c.sf_b, c.sf_t, c.sC_b, c.sC_t, c.sc_b, c.sc_t, c.sCfin_b, c.scfin_b, c.sdF_b, c.sdF_t, c.sdf_b,
+                   c.sdf_t, c.sdC_b, c.sdC_t, c.sdc_b, c.sdc_t, c.sdCfin_b, c.sdcfin_b, c.sdx0_b})
+        if (s < 0) return TFMPC_ERR_ARG;
+    return TFMPC_OK;
+}
+
+// What of VjpBase<S> does not depend on the precision's costates: the model, the final cost, the trajectory, the upstream
+// gradients, the adjoint's arrays in the workspace w, the outputs and the status.  P, a0 and poison_mask are the caller's.
+template <class S>
+void vjp_fill_base(VjpBase<S> &a, const VjpCall<S> &c, S *w, const VjpPrefix &L)
+{
+    a.B = c.B; a.n = c.n; a.m = c.m; a.T = c.T;
+    a.F = c.F; a.sF_b = c.sF_b; a.sF_t = c.sF_t;
+    a.C = c.C; a.sC_b = c.sC_b; a.sC_t = c.sC_t;
+    a.c = c.c; a.sc_b = c.sc_b; a.sc_t = c.sc_t;
+    a.dflt = c.Cfin == nullptr;
+    a.states = c.states; a.actions = c.actions; a.gx = c.g_states; a.gu = c.g_actions; a.gc = c.g_costs;
+    a.dS = w + L.dS; a.dA = w + L.dA; a.ct = w + L.ct; a.cT = w + L.cT;
+    a.status = c.status;
+    if (a.dflt) {                    // the fold's copy of C_{T-1}[:n,:n]; c_{T-1}[:n], contiguous in c
+        a.Cf = w + L.Cfe; a.sCf_b = c.sC_b ? (long)c.n * c.n : 0;
+        a.cf = c.c + (size_t)(c.T - 1) * c.sc_t; a.scf_b = c.sc_b;
+    } else {
+        a.Cf = c.Cfin; a.sCf_b = c.sCfin_b;
+        a.cf = c.cfin; a.scf_b = c.scfin_b;
+    }
+    const OutT<S> outs[kKinds] = {{c.dF, c.sdF_b, c.sdF_t}, {c.df, c.sdf_b, c.sdf_t}, {c.dC, c.sdC_b, c.sdC_t}, {c.dc, c.sdc_b, c.sdc_t},
+                                  {c.dCfin, c.sdCfin_b, 0}, {c.dcfin, c.sdcfin_b, 0}, {c.dx0, c.sdx0_b, 0}};
+    for (int k = 0; k < kKinds; ++k) a.o[k] = outs[k];
+}
+
+// The bounds' operands; mask, Rlo, Rhi: the caller's places in its workspace.
+template <class S>
+void box_fill(BoxArgsT<S> &bx, const BoxCall<S> &box, uint32_t *mask, S *Rlo, S *Rhi)
+{
+    bx.low = box.low; bx.slo_b = box.slo_b; bx.slo_t = box.slo_t;
+    bx.high = box.high; bx.shi_b = box.shi_b; bx.shi_t = box.shi_t;
+    bx.mask = mask; bx.mask_out = box.clamp_mask;
+    bx.Rlo = Rlo; bx.Rhi = Rhi;
+    bx.olo = OutT<S>{box.dlow, box.sdlo_b, box.sdlo_t};
+    bx.ohi = OutT<S>{box.dhigh, box.sdhi_b, box.sdhi_t};
 }
 
 }  // namespace tfmpc
