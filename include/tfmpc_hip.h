@@ -535,6 +535,23 @@ int tfmpc_lqr_steady_state_vjp_f32(int B, int n, int m,
                                    float *dF, long sdF_b, float *df, long sdf_b, float *dC, long sdC_b, float *dc, long sdc_b,
                                    int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* tfmpc_lqr_steady_state_vjp_f32 in double, for the K, k, P, p of tfmpc_lqr_steady_state_f64: the
+ * same sequence, argument rules, status bits and NaN rows, every operand, upstream gradient and output double,
+ * products on the f64 matrix cores, the batch sums in the same fixed order with double accumulators.  tol = 0.0 selects
+ * 4 DBL_EPSILON.  n <= 16, m <= 16: "ss_vjp_f64_wave16"; n <= 32, m <= 32: "ss_vjp_f64_wave32" (118 KiB of dynamic LDS,
+ * one wave per CU); beyond: TFMPC_ERR_UNSUPPORTED.  workspace: tfmpc_lqr_steady_state_vjp_workspace_bytes_f64(B, n, m)
+ * bytes (the fp32 plan's element counts, 8 bytes each). */
+size_t tfmpc_lqr_steady_state_vjp_workspace_bytes_f64(int B, int n, int m);
+const char *tfmpc_lqr_steady_state_vjp_kernel_name_f64(int n, int m);
+int tfmpc_lqr_steady_state_vjp_f64(int B, int n, int m,
+                                   const double *F, long sF_b, const double *f, long sf_b,
+                                   const double *C, long sC_b, const double *c, long sc_b,
+                                   const double *K, const double *k, const double *P, const double *p, const int32_t *fwd_status,
+                                   const double *gK, const double *gk, const double *gP, const double *gp,
+                                   int max_iter, double tol,
+                                   double *dF, long sdF_b, double *df, long sdf_b, double *dC, long sdC_b, double *dc, long sdc_b,
+                                   int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* --------------------------------------------------------------- iLQR --------
  * Control-limited iLQR (tfmpc/solvers/ilqr.py) over the reference's differentiable
  * environments (tfmpc/envs).  An environment is described by a kind tag plus

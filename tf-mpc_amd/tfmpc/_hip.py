@@ -105,6 +105,11 @@ _SIGNATURES.update({
     # status workspace workspace_bytes stream
     "tfmpc_lqr_steady_state_vjp_f32": (_I, [_I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                             _I, ctypes.c_float, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _Z, _P]),
+    # ... in double: the same arguments, tol a double
+    "tfmpc_lqr_steady_state_vjp_workspace_bytes_f64": (_Z, [_I, _I, _I]),
+    "tfmpc_lqr_steady_state_vjp_kernel_name_f64": (ctypes.c_char_p, [_I, _I]),
+    "tfmpc_lqr_steady_state_vjp_f64": (_I, [_I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                            _I, ctypes.c_double, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _Z, _P]),
 })
 
 

@@ -123,8 +123,9 @@ def _steady_state_dtype(dtype):
     return torch.float64 if dtype == torch.float64 else torch.float32
 
 
-_NO_F64_GRAD = ("gradients of the steady state are fp32 only: detach the operands (or call under torch.no_grad()) for "
-                "dtype=torch.float64, or use the fp32 steady_state(differentiable=True)")
+_NO_F64_GRAD = ("gradients of the double steady state are an opt-in of the functional form: call "
+                "tfmpc.solvers.lqr_steady_state(..., dtype=torch.float64, differentiable=True); otherwise detach the operands "
+                "(or call under torch.no_grad()) for dtype=torch.float64, or use the fp32 steady_state(differentiable=True)")
 
 
 def _steady_state_launch_f64(F, f, C, c, batch_size, max_iter, tol):
@@ -154,8 +155,9 @@ def steady_state_f64(F, f, C, c, max_iter=None, tol=None, device=None):
     """The double-precision steady state of the caller's operands (``tfmpc_lqr_steady_state_f64``):
     tensors or numpy arrays of any dtype are taken to float64 directly, never through fp32.  Returns a
     :class:`SteadyState` of float64 tensors (``iterations``, ``status`` int32).  ``C`` must be symmetric to 1e-12 of its
-    largest entry.  Gradients are not served in double: an operand that requires grad while autograd is recording
-    raises ``NotImplementedError``."""
+    largest entry.  This is the call without gradients: an operand that requires grad while autograd is recording
+    raises ``NotImplementedError`` (``tfmpc.solvers.lqr_steady_state(..., dtype=torch.float64, differentiable=True)``
+    serves them)."""
     if tvlqr_grad.wants_grad(*(a for a in (F, f, C, c) if isinstance(a, torch.Tensor))):
         raise NotImplementedError(_NO_F64_GRAD)
     device = torch.device(device) if device is not None else _hip.default_device()
@@ -428,8 +430,10 @@ class LQR:
         STORES, which are fp32, and returns the double solution of that fp32-rounded problem as float64 tensors
         (``tfmpc_lqr_steady_state_f64``; ``tol`` then defaults to 4 double ulps): the terminal cost for
         ``TimeVaryingLQR.from_lqr(lqr, T, ss.P, ss.p, dtype=torch.float64)``.  For operands that are double to begin
-        with, use ``tfmpc.solvers.lqr_steady_state(..., dtype=torch.float64)``.  Gradients are fp32 only: with
-        ``torch.float64``, ``differentiable=True`` or an operand that requires grad raises ``NotImplementedError``."""
+        with, use ``tfmpc.solvers.lqr_steady_state(..., dtype=torch.float64)``.  This method's gradients are fp32 only
+        (double gradients with respect to fp32-rounded stored operands would be a different contract): with
+        ``torch.float64``, ``differentiable=True`` or an operand that requires grad raises ``NotImplementedError``;
+        ``tfmpc.solvers.lqr_steady_state(..., dtype=torch.float64, differentiable=True)`` serves them."""
         double = _steady_state_dtype(dtype) == torch.float64
         if not self.symmetric_cost:
             raise NotImplementedError("the steady state is served for a symmetric C only")

@@ -10,7 +10,13 @@
 
 Instances are a pool of 512 distinct draws, instance b holding its own copy of pool[b % 512].  Kernel times are the
 ABI calls with preallocated buffers.  Prints one JSON object (median / min of --reps timed calls after --warmup).
-Usage: python tools/lqr_steady_state_grad_rate.py [--reps 20] [--warmup 3] [--out file.json]"""
+
+--dtype float64 times the double gradients (tfmpc_lqr_steady_state_vjp_f64) on lines (a), (b), (c), the
+same numbers upcast: the double VJP, the fp32 VJP and the double forward take turns in one process, one timed call each
+per round, --reps rounds after --warmup; the whole measurement runs twice, and the gap between the two medians is the
+spread a ratio of this file can be trusted to.  Writes the JSON line to --out (default
+profiles/lqr_steady_state_grad_f64_rate.json).
+Usage: python tools/lqr_steady_state_grad_rate.py [--dtype float64] [--reps 20] [--warmup 3] [--out file.json]"""
 import argparse
 import json
 import os
@@ -26,7 +32,7 @@ for p in (ROOT, os.path.join(ROOT, "tf-mpc_amd"), os.path.join(ROOT, "tests")):
 
 import lqr_steady_state_ref as ssref  # noqa: E402
 from tfmpc import _hip  # noqa: E402
-from tfmpc.solvers.lqr import LQR  # noqa: E402
+from tfmpc.solvers.lqr import LQR, _steady_state_launch_f64  # noqa: E402
 
 B, N, M, POOL = 65536, 16, 8, 512
 
@@ -74,6 +80,73 @@ class Vjp:
                                                      *(_hip.ptr(u) for u in self.up), 0, 0.0, *outs, _hip.ptr(self.status),
                                                      _hip.ptr(self.ws), self.ws_bytes, _hip.stream())
         _hip.check(rc, "tfmpc_lqr_steady_state_vjp_f32")
+
+
+class Vjp64:
+    """Preallocated buffers of one tfmpc_lqr_steady_state_vjp_f64 call on the double `model` (F, f, C, c) and its forward `ss`."""
+
+    def __init__(self, model, ss, up, summed=()):
+        self.lib = _hip.load()
+        self.model, self.ss = model, ss
+        n, m, d = N, M, N + M
+        self.up = [u.double() for u in up]
+        sizes = dict(F=n * d, f=n, C=d * d, c=d)
+        self.outs = []
+        for name in ("F", "f", "C", "c"):
+            t = torch.empty((sizes[name] if name in summed else B * sizes[name],), device="cuda", dtype=torch.float64)
+            self.outs += [t, 0 if name in summed else sizes[name]]
+        self.ws_bytes = int(self.lib.tfmpc_lqr_steady_state_vjp_workspace_bytes_f64(B, n, m)) if summed else 0
+        self.ws = torch.empty(((self.ws_bytes + 7) // 8,), device="cuda", dtype=torch.float64) if summed else None
+        self.status = torch.empty((B,), dtype=torch.int32, device="cuda")
+
+    def __call__(self):
+        model = []
+        for t in self.model:
+            model += [_hip.ptr(t), t.stride(0) if t.dim() == 3 else 0]
+        outs = [(_hip.ptr(x) if i % 2 == 0 else x) for i, x in enumerate(self.outs)]
+        rc = self.lib.tfmpc_lqr_steady_state_vjp_f64(B, N, M, *model, *(_hip.ptr(t) for t in self.ss[:4]), _hip.ptr(self.ss[5]),
+                                                     *(_hip.ptr(u) for u in self.up), 0, 0.0, *outs, _hip.ptr(self.status),
+                                                     _hip.ptr(self.ws), self.ws_bytes, _hip.stream())
+        _hip.check(rc, "tfmpc_lqr_steady_state_vjp_f64")
+
+
+def taking_turns(fns, reps, warmup):
+    """name -> median ms of `reps` timed calls, the functions called one after the other in every round."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {name: [] for name in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts[name].append(e0.elapsed_time(e1))
+    return {name: float(np.median(v)) for name, v in ts.items()}
+
+
+def line_f64(name, lqr, reps, warmup, summed=()):
+    ss32 = lqr._steady_state_launch(0, 0.0)
+    model = [t.double().contiguous() for t in (lqr.F, lqr.f, lqr.C, lqr.c)]
+    forward = lambda: _steady_state_launch_f64(*model, lqr.batch_size, 0, 0.0)      # noqa: E731
+    ss64 = forward()
+    v32 = Vjp(lqr, ss32, summed)
+    v64 = Vjp64(model, ss64, v32.up, summed)
+    v64()
+    torch.cuda.synchronize()
+    fns = {"vjp_f64": v64, "vjp_f32": v32, "forward_f64": forward}
+    first, second = taking_turns(fns, reps, warmup), taking_turns(fns, reps, warmup)
+    out = {f"{name}_flagged": int((ss64[5] != 0).sum()), f"{name}_backward_flagged": int((v64.status != 0).sum())}
+    for key in fns:
+        out[f"{name}_{key}_ms"] = first[key]
+        out[f"{name}_{key}_repeat_ms"] = second[key]
+        out[f"{name}_{key}_spread"] = abs(first[key] - second[key]) / min(first[key], second[key])
+    out[f"{name}_backward_over_forward_f64"] = first["vjp_f64"] / first["forward_f64"]
+    out[f"{name}_vjp_f64_over_vjp_f32"] = first["vjp_f64"] / first["vjp_f32"]
+    return out
 
 
 def line(name, lqr, reps, warmup, summed=()):
@@ -159,12 +232,29 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out")
+    ap.add_argument("--dtype", choices=("float32", "float64"), default="float32")
     args = ap.parse_args()
     _hip.require_gpu()
     torch.cuda.set_device(0)
     idx = np.arange(B) % POOL
     a = ssref.make_lqr_batch(N, M, POOL, seed=0)
     d = ssref.damped_workload(N, M, POOL, seed=0)
+    if args.dtype == "float64":
+        lib = _hip.load()
+        out = {"B": B, "n": N, "m": M, "kernel": lib.tfmpc_lqr_steady_state_vjp_kernel_name_f64(N, M).decode(),
+               "kernel_f32": lib.tfmpc_lqr_steady_state_vjp_kernel_name(N, M).decode(),
+               "forward_kernel": lib.tfmpc_lqr_steady_state_kernel_name_f64(N, M).decode(), "reps": args.reps,
+               "warmup": args.warmup, "order": "vjp_f64, vjp_f32, forward_f64 take turns; two runs of reps rounds"}
+        out.update(line_f64("a_make_lqr", LQR(*(x[idx] for x in a), device="cuda", symmetric=True), args.reps, args.warmup))
+        out.update(line_f64("b_damped", LQR(*(x[idx] for x in d), device="cuda", symmetric=True), args.reps, args.warmup))
+        goals = np.random.default_rng(1).normal(size=(B, N + M)).astype(np.float32)
+        shared = LQR(a[0][0], a[1][0], a[2][0], goals, device="cuda", symmetric=True)
+        out.update(line_f64("c_shared", shared, args.reps, args.warmup, summed=("F", "f", "C")))
+        text = json.dumps(out)
+        print(text)
+        with open(args.out or os.path.join(ROOT, "profiles", "lqr_steady_state_grad_f64_rate.json"), "w") as fh:
+            fh.write(text + "\n")
+        return
     out = {"B": B, "n": N, "m": M, "kernel": _hip.load().tfmpc_lqr_steady_state_vjp_kernel_name(N, M).decode(), "reps": args.reps}
     out.update(line("a_make_lqr", LQR(*(x[idx] for x in a), device="cuda", symmetric=True), args.reps, args.warmup))
     out.update(line("b_damped", LQR(*(x[idx] for x in d), device="cuda", symmetric=True), args.reps, args.warmup))
