@@ -360,6 +360,25 @@ int tfmpc_tvlqr_backward_vjp_f32(int B, int n, int m, int T,
                                  float *dCfin, long sdCfin_b, float *dcfin, long sdcfin_b,
                                  int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* tfmpc_tvlqr_backward_vjp_f32 in double, for the K, k, V, v of tfmpc_tvlqr_backward_f64: the same
+ * sweep, argument rules, strides, stride-0 sums, status bits and NaN rows, every operand, upstream gradient and output
+ * double, products on the f64 matrix cores.  The batch sum runs in double over chunks of 64 instances, then a tree over
+ * the chunks (the order of tfmpc_lqr_steady_state_vjp_f64).  n <= 16, m <= 16: "tvb_vjp_f64_wave16"; n <= 32, m <= 32:
+ * "tvb_vjp_f64_wave32" (141.5 KiB of dynamic LDS, one wave per CU); beyond: TFMPC_ERR_UNSUPPORTED.  workspace:
+ * tfmpc_tvlqr_backward_vjp_workspace_bytes_f64(B, n, m, T) bytes (the plan's element counts, 8 bytes each). */
+size_t tfmpc_tvlqr_backward_vjp_workspace_bytes_f64(int B, int n, int m, int T);
+const char *tfmpc_tvlqr_backward_vjp_kernel_name_f64(int n, int m, int T);
+int tfmpc_tvlqr_backward_vjp_f64(int B, int n, int m, int T,
+                                 const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                                 const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                                 const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                                 const double *K, const double *k, const double *V, const double *v, const int32_t *fwd_status,
+                                 const double *gK, const double *gk, const double *gV, const double *gv, const double *gconst,
+                                 double *dF, long sdF_b, long sdF_t, double *df, long sdf_b, long sdf_t,
+                                 double *dC, long sdC_b, long sdC_t, double *dc, long sdc_b, long sdc_t,
+                                 double *dCfin, long sdCfin_b, double *dcfin, long sdcfin_b,
+                                 int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------- control-limited TV-LQR gradients --------
  * tfmpc_tvlqr_vjp_f32 at the optimum of the CONTROL-LIMITED problem, low <= u_t <= high.  low, high:
  * [m] per (b, t) with a batch and a time stride in elements (0 = shared), +-inf allowed.  Control i of instance b is HELD

@@ -82,10 +82,16 @@ inline int batch_sum_run(const BatchSumPlan &p, T *w, T *const *outs, const long
         hipLaunchKernelGGL(batch_sum_stage1<CHUNK>, dim3(chunks * slices), dim3(kSumThreads), 0, s, w + p.rec_off[q], p.B, nE,
                            w + p.partial_off);
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
-        if constexpr (ORDER == kSumTree)
-            hipLaunchKernelGGL(batch_sum_stage2_tree<kSumThreads>, dim3((unsigned)nE), dim3(kSumThreads), 0, s, w + p.partial_off,
-                               chunks, nE, outs[q]);
-        else
+        if constexpr (ORDER == kSumTree) {
+            // one launch where the slots are dense in the output; else a launch per slot (its columns of the partial sums)
+            const bool dense = p.slots[q] == 1 || st[q] == (long)p.size[q];
+            const int launches = dense ? 1 : p.slots[q];
+            for (int t = 0; t < launches; ++t) {
+                hipLaunchKernelGGL(batch_sum_stage2_tree<kSumThreads>, dim3((unsigned)(dense ? nE : p.size[q])), dim3(kSumThreads), 0,
+                                   s, w + p.partial_off + (size_t)t * p.size[q], chunks, nE, outs[q] + (size_t)t * st[q]);
+                if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;
+            }
+        } else
             hipLaunchKernelGGL(batch_sum_stage2_in_order<kSumThreads>, dim3(slices), dim3(kSumThreads), 0, s, w + p.partial_off,
                                chunks, nE, p.size[q], outs[q], st[q]);
         if (hipGetLastError() != hipSuccess) return TFMPC_ERR_LAUNCH;

@@ -92,6 +92,10 @@ _SIGNATURES.update({
     # K k V v fwd_status, gK gk gV gv gconst, dF df dC dc (+ batch, time strides), dCfin dcfin (+ batch stride),
     # status workspace workspace_bytes stream
     "tfmpc_tvlqr_backward_vjp_f32": (_I, _TV_MODEL + [_P] * 5 + [_P] * 5 + [_P, _L, _L] * 4 + [_P, _L] * 2 + [_P, _P, _Z, _P]),
+    # ... in double: the same arguments, every float * a double *
+    "tfmpc_tvlqr_backward_vjp_workspace_bytes_f64": (_Z, [_I, _I, _I, _I]),
+    "tfmpc_tvlqr_backward_vjp_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I]),
+    "tfmpc_tvlqr_backward_vjp_f64": (_I, _TV_MODEL + [_P] * 5 + [_P] * 5 + [_P, _L, _L] * 4 + [_P, _L] * 2 + [_P, _P, _Z, _P]),
     "tfmpc_lqr_steady_state_kernel_name": (ctypes.c_char_p, [_I, _I]),
     # B n m, F f C c (+ batch strides), max_iter tol, K k P p, iterations status stream
     "tfmpc_lqr_steady_state_f32": (_I, [_I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _I, ctypes.c_float,

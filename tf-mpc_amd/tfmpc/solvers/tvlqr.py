@@ -13,7 +13,8 @@ Precision: the default ``dtype=torch.float32`` casts every operand to fp32, floa
 ``dtype=torch.float64`` for the double-precision kernels (``tfmpc_tvlqr_*_f64``, DESIGN.md 3.14, n <= 32 and m <= 32):
 operands, ``x0`` and every output then stay in double.  Gradients of the double solve are opt-in:
 ``solve(x0, differentiable=True)`` / ``solve_tensors(x0, differentiable=True)`` (``tfmpc_tvlqr_vjp_f64``, DESIGN.md 3.15);
-the Riccati recursion's gradients (``backward(differentiable=True)``) are served in fp32 only.
+the Riccati recursion's gradients (``backward(differentiable=True)``) are served in fp32 only by the method; in double they
+are :func:`tfmpc.solvers.tvlqr_backward` with ``dtype=torch.float64`` (``tfmpc_tvlqr_backward_vjp_f64``).
 
 A few long horizons (B <= 64 or so, T in the hundreds or thousands): ``solve_time_parallel`` /
 :func:`tvlqr_solve_time_parallel` cut the horizon into segments that are worked on concurrently
@@ -117,11 +118,13 @@ class TimeVaryingLQR:
         return _as_dtype(a, self.device, self.dtype)
 
     def _refuse_grad(self, *more, solve=False):
-        """Double-precision gradients are opt-in (and the Riccati recursion has none): say so before any launch, never
-        downcast."""
+        """Double-precision gradients are opt-in (the Riccati recursion's through ``tvlqr_backward(..., dtype=torch.float64)``
+        only): say so before any launch, never downcast."""
         if self.dtype == torch.float64 and tvlqr_grad.wants_grad(*self._sources, *more):
             how = ("pass differentiable=True to solve / solve_tensors for the double-precision gradients, build the problem "
-                   "with dtype=torch.float32" if solve else "build the problem with dtype=torch.float32")
+                   "with dtype=torch.float32" if solve else
+                   "build the problem with dtype=torch.float32, call tfmpc.solvers.tvlqr_backward(..., dtype=torch.float64) for the "
+                   "Riccati recursion's gradients in double")
             raise NotImplementedError(f"gradients of the time-varying LQR in double are not served by this call: {how}, or "
                                       "detach the operands and x0 for a dtype=torch.float64 solve")
 
@@ -264,7 +267,8 @@ class TimeVaryingLQR:
         operand requires grad, their tensors are in the autograd graph, with gradients from
         ``tfmpc_tvlqr_backward_vjp_f32`` (tfmpc/solvers/tvlqr_backward_grad.py); the backward pass's
         per-instance status goes to ``last_grad_status``.  The outputs are the same bits as without grad.
-        With ``dtype=torch.float64`` that request raises ``NotImplementedError`` (gradients are fp32 only)."""
+        With ``dtype=torch.float64`` that request raises ``NotImplementedError`` (this method's gradients are fp32 only):
+        the double gradients are ``tfmpc.solvers.tvlqr_backward(..., dtype=torch.float64)``."""
         if differentiable:
             self._refuse_grad()
         if differentiable and tvlqr_grad.wants_grad(*self._sources):
