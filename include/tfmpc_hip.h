@@ -71,7 +71,7 @@ int tfmpc_version(void);
  * line search of the 2 x 2 lane-group kernel keep their candidate trajectory in the workspace; a pass that adopts another one rolls it out once
  * more -- same bits, for tests and A/B timing), TFMPC_BOX_SPECULATE (off | n, default 0: after n rejected passes in a row the helper team of a
  * control-limited instance runs the backward passes of its next passes beside its own -- same bits), TFMPC_TVLQR_TP_PHASES (1 | 2: tfmpc_tvlqr_solve_time_parallel_f64
- * returns TFMPC_TVLQR_TP_STOPPED (1, not TFMPC_OK) after its condense / its stitch launch and writes no output -- for timing the phases only) are read ONCE per process, at the first use of the library; afterwards only
+ * returns TFMPC_TVLQR_TP_STOPPED (1, not TFMPC_OK) after its condense / its stitch launch and writes no output -- for timing the phases only; 1 .. 6: tfmpc_tvlqr_vjp_time_parallel_f64 likewise, after the launches its block lists) are read ONCE per process, at the first use of the library; afterwards only
  * this call changes them (value NULL or "" = back to the dispatcher's own choice).  Returns TFMPC_ERR_ARG
  * for an unknown name.  Process-wide; not meant to be flipped while other threads launch. */
 int tfmpc_set_option(const char *name, const char *value);
@@ -330,6 +330,44 @@ int tfmpc_tvlqr_vjp_f64(int B, int n, int m, int T,
                         double *dC, long sdC_b, long sdC_t, double *dc, long sdc_b, long sdc_t,
                         double *dCfin, long sdCfin_b, double *dcfin, long sdcfin_b, double *dx0, long sdx0_b,
                         int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------- TV-LQR gradients, double precision, time-parallel (segmented adjoint) --------
+ * tfmpc_tvlqr_vjp_f64's contract and argument order for a FEW LONG horizons, the companion of
+ * tfmpc_tvlqr_solve_time_parallel_f64.  Two more inputs are REQUIRED beside v: the forward's K[B][T][m][n] and
+ * V[B][T][n][n] (that solve writes both on request).  The adjoint problem has the forward's F, C, C_fin, hence its gains
+ * and value function; its vector part is two affine recursions in the closed-loop transition Phi_t = F_t [I; K_t], which
+ * are condensed per segment to one n x n matrix and one offset per direction, stitched with P matrix-vector products
+ * and expanded concurrently.  No Riccati step is repeated; the only elimination is Q_uu,t = C_t[n:,n:] + B_t' V_{t+1} B_t,
+ * without pivoting, once per (b, t).  `segments` follows `status`: clamped to T, len = ceil(T / segments),
+ * P = ceil(T / len) as in tfmpc_tvlqr_solve_time_parallel_f64.  With P == 1 the call forwards to tfmpc_tvlqr_vjp_f64,
+ * ignores K and V and returns its bits (and that call's workspace rule applies).
+ * Checks, before any launch: tfmpc_tvlqr_vjp_f64's in its order, with segments < 1 (TFMPC_ERR_ARG) after the shape
+ * tests and K or V NULL (TFMPC_ERR_ARG, P > 1) after v; a workspace that is not 8-byte aligned is TFMPC_ERR_ARG.
+ * status[b] is the OR over the instance's steps: TFMPC_ST_NOT_PD for a non-positive pivot of Q_uu,t; an instance with any
+ * bit set has NaN in its own gradient rows and in every batch-summed gradient.  No atomics, every sum in a fixed order:
+ * an instance's bits depend on neither B nor its position, and repeated calls give identical bits.  A per-instance
+ * output with time stride 0 is accumulated by tfmpc_tvlqr_vjp_f64's one-wave-per-instance costate walk, which stays
+ * serial in T.  With up(x) = x rounded up to a multiple of 64, d = n + m, chunks = ceil(B / 256), the workspace for P > 1
+ * holds
+ *   8 * [ up(B T d) + 2 up(B n) + up(B n n) + up(B (T+1) n) + up(B T m) + up(B (T+1))
+ *         + up(B T n n) + up(B T n) + up(B T m) + up(B T n m) + up(B T n) + up(B T n) + up(2 B T n)
+ *         + up(chunks T (n d + n + d d + d)) + up(B P n n) + 4 up(B P n) + up(ceil(B T / 2)) ]  bytes
+ * (fold and adjoint trajectory; Phi, a, r, E, w per step; v~; the costate records; the partial sums; M, beta, gamma and
+ * the boundary vectors per segment; one status word per step): no V, no gains and no solve workspace of its own.
+ * TFMPC_TVLQR_TP_PHASES = 1 .. 6 stops this call after the step kernel / the condense / the backward stitch / the
+ * backward expand / the forward stitch / the forward expand (TFMPC_TVLQR_TP_STOPPED, no output written; timing only). */
+size_t tfmpc_tvlqr_vjp_time_parallel_workspace_bytes_f64(int B, int n, int m, int T, int segments);
+int tfmpc_tvlqr_vjp_time_parallel_f64(int B, int n, int m, int T,
+                                      const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                                      const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                                      const double *Cfin, long sCfin_b, const double *cfin, long scfin_b,
+                                      const double *states, const double *actions, const double *v,
+                                      const double *K, const double *V,
+                                      const double *g_states, const double *g_actions, const double *g_costs,
+                                      double *dF, long sdF_b, long sdF_t, double *df, long sdf_b, long sdf_t,
+                                      double *dC, long sdC_b, long sdC_t, double *dc, long sdc_b, long sdc_t,
+                                      double *dCfin, long sdCfin_b, double *dcfin, long sdcfin_b, double *dx0, long sdx0_b,
+                                      int32_t *status, int segments, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------- gradients of the Riccati recursion --------
  * Vector-Jacobian product of tfmpc_tvlqr_backward_f32: given the recursion's K[B][T][m][n], k[B][T][m],

@@ -570,6 +570,14 @@ inline size_t vjp_partial_elems(int B, int n, int m, int T)
     return up64(((size_t)B + kChunk - 1) / kChunk * T * (size_t)steps_E(n, n + m));
 }
 
+// The plain double VJP around its adjoint solve (tvlqr_vjp_f64.hip), for a caller that brings the adjoint trajectory itself
+// (tvlqr_vjp_time_parallel_f64.hip); w: the caller's workspace, which starts with VjpPrefix.  The fold fills
+// ct, cT, Cfe, zer.  The costates and batch sums read dS, dA, the forward's v [B][T][n], V [B][T][n][n] and v~ [B][T][n] of the
+// adjoint problem, and use P [B][T][2n] and partial (vjp_partial_elems) as scratch.
+int tvlqr_vjp_f64_fold_launch(const VjpCall<double> &c, double *w, const VjpPrefix &L);
+int tvlqr_vjp_f64_costates_launch(const VjpCall<double> &c, double *w, const VjpPrefix &L, const double *v, const double *V,
+                                  const double *vt, double *P, double *partial);
+
 // ---- the argument contract of the four entries -------------------------------------------------------------------------
 // The checks that follow an entry's own shape test and its B == 0 return, in the order every entry has always made them.
 // fits: the precision's own refusals (LDS sizes, the held-set word), which come after the grid limits and before the

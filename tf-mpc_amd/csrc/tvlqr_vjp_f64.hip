@@ -39,6 +39,9 @@
 //                           r_t[n + i] = (C_t dz_t + g_t + F_t^T dlam_{t+1})[n + i], the gradient of the bound the control
 //                           sits on (low when it equals both); free controls and the other bound get exact zeros.
 //   4. the batch sums       vjp_shared_sums<double> for the model's gradients, box_shared_sums<double> for the bounds'.
+// Launches 1 and 3 - 4 of the plain VJP can also be enqueued from outside (tvlqr_vjp_f64_fold_launch,
+// tvlqr_vjp_f64_costates_launch; tvlqr_vjp_common.h): the segmented adjoint of the time-parallel solve brings its own v~, dx,
+// du and the forward's V (tvlqr_vjp_time_parallel_f64.hip).
 // An instance with a status bit set contributes NaN (its own rows, dlow / dhigh included, and every batch sum that
 // includes it).  The build is -ffp-contract=off: every fused multiply-add is a written fma().  No scratch memory.
 #include <hip/hip_runtime.h>
@@ -299,6 +302,32 @@ BoxLayout box_layout(int B, int n, int m, int T)
     return L;
 }
 
+// VjpArgs of a call whose workspace w starts with VjpPrefix: the forward's v (or v^m), the adjoint's V and v~, the records
+VjpArgs make_args(const VjpCall<double> &c, double *w, const VjpPrefix &L, const double *v, const double *V, const double *vt, double *P)
+{
+    VjpArgs a{};
+    vjp_fill_base<double>(a, c, w, L);
+    a.v = v;
+    a.V = V; a.vt = vt;
+    a.poison_mask = ~0;
+    a.P = P;
+    a.a0 = const_cast<double *>(vt); a.sa0_b = (long)c.T * c.n;
+    return a;
+}
+
+// dF or df shared by the batch: the costate kernel leaves a record (dlam_{t+1}, lam_{t+1}) per (b, t)
+bool wants_records(const VjpCall<double> &c) { return (c.dF && !c.sdF_b) || (c.df && !c.sdf_b); }
+
+// The model's gradients with a batch stride: emitted per (b, t), or per instance in time order (time stride 0)
+void model_wants(const VjpArgs &a, unsigned &per_step, unsigned &in_time)
+{
+    for (int k = kF; k < kKinds; ++k) {
+        if (!a.o[k].p || !a.o[k].sb) continue;
+        if (k <= kc && a.o[k].st == 0 && a.T > 1) in_time |= 1u << k;
+        else per_step |= 1u << k;
+    }
+}
+
 // Both entries.  Plain (box == NULL): v is the forward solve's, from the caller.  Control-limited: v is not given; the
 // second masked sweep computes v^m.  The checks and the fill of VjpArgs that do not depend on the precision are
 // tvlqr_vjp_common.h's.
@@ -317,13 +346,7 @@ int vjp_f64_impl(const VjpCall<double> &c, const double *v, const BoxCall<double
     hipStream_t s = static_cast<hipStream_t>(c.stream);
     double *w = static_cast<double *>(c.workspace);
 
-    VjpArgs a{};
-    vjp_fill_base<double>(a, c, w, L);
-    a.v = box ? w + XL.vm : v;
-    a.V = w + L.V; a.vt = w + L.vt;
-    a.poison_mask = ~0;
-    a.P = w + L.P;
-    a.a0 = w + L.vt; a.sa0_b = (long)T * n;
+    const VjpArgs a = make_args(c, w, L, box ? w + XL.vm : v, w + L.V, w + L.vt, w + L.P);
     BoxTail<true> bx{};
     if (box) {
         box_fill<double>(bx, *box, reinterpret_cast<uint32_t *>(w + XL.mask), w + XL.Rlo, w + XL.Rhi);
@@ -362,13 +385,9 @@ int vjp_f64_impl(const VjpCall<double> &c, const double *v, const BoxCall<double
         if (rc != TFMPC_OK) return rc;
     }
     // 3. costates and the gradients with a batch stride; batch-shared bounds leave a record per (b, t)
-    const bool reduce_F = (c.dF && !c.sdF_b) || (c.df && !c.sdf_b);
+    const bool reduce_F = wants_records(c);
     unsigned per_step = 0, in_time = 0;
-    for (int k = kF; k < kKinds; ++k) {
-        if (!a.o[k].p || !a.o[k].sb) continue;
-        if (k <= kc && a.o[k].st == 0 && T > 1) in_time |= 1u << k;
-        else per_step |= 1u << k;
-    }
+    model_wants(a, per_step, in_time);
     const Out bo[2] = {bx.olo, bx.ohi};              // (plain: both NULL)
     for (int k = 0; k < 2; ++k) {
         if (!bo[k].p) continue;
@@ -385,6 +404,30 @@ int vjp_f64_impl(const VjpCall<double> &c, const double *v, const BoxCall<double
 }
 
 }  // namespace
+
+namespace tfmpc {
+
+int tvlqr_vjp_f64_fold_launch(const VjpCall<double> &c, double *w, const VjpPrefix &L)
+{
+    const VjpArgs a = make_args(c, w, L, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(vjp_fold_kernel, dim3((unsigned)((size_t)c.B * (c.T + 1))), dim3(kWaveThreads),
+                       fold_smem_elems(c.n, c.m) * sizeof(double), static_cast<hipStream_t>(c.stream), a, w + L.ct, w + L.cT,
+                       w + L.Cfe, w + L.zer);
+    return hipGetLastError() == hipSuccess ? TFMPC_OK : TFMPC_ERR_LAUNCH;
+}
+
+int tvlqr_vjp_f64_costates_launch(const VjpCall<double> &c, double *w, const VjpPrefix &L, const double *v, const double *V,
+                                  const double *vt, double *P, double *partial)
+{
+    const VjpArgs a = make_args(c, w, L, v, V, vt, P);
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    unsigned per_step = 0, in_time = 0;
+    model_wants(a, per_step, in_time);
+    if (const int rc = launch_costates<false>(a, per_step, in_time, wants_records(c), {}, s); rc != TFMPC_OK) return rc;
+    return vjp_shared_sums<double>(a, partial, s);
+}
+
+}  // namespace tfmpc
 
 extern "C" {
 

@@ -67,6 +67,10 @@ _SIGNATURES.update({
     "tfmpc_tvlqr_vjp_workspace_bytes_f64": (_Z, [_I, _I, _I, _I]),
     # ... states actions v, then as tfmpc_tvlqr_vjp_f32
     "tfmpc_tvlqr_vjp_f64": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3 + [_P, _P, _Z, _P]),
+    # the segmented adjoint: ... states actions v K V, then as tfmpc_tvlqr_vjp_f64 with `segments` after status
+    "tfmpc_tvlqr_vjp_time_parallel_workspace_bytes_f64": (_Z, [_I, _I, _I, _I, _I]),
+    "tfmpc_tvlqr_vjp_time_parallel_f64": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3
+                                          + [_P, _I, _P, _Z, _P]),
     "tfmpc_tvlqr_box_vjp_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "tfmpc_tvlqr_box_vjp_kernel_name": (ctypes.c_char_p, [_I, _I, _I]),
     # the VJP's arguments with low high (+ batch, time strides) after the model, and dlow dhigh (+ batch, time strides),

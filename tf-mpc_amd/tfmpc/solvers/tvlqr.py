@@ -18,7 +18,9 @@ are :func:`tfmpc.solvers.tvlqr_backward` with ``dtype=torch.float64`` (``tfmpc_t
 
 A few long horizons (B <= 64 or so, T in the hundreds or thousands): ``solve_time_parallel`` /
 :func:`tvlqr_solve_time_parallel` cut the horizon into segments that are worked on concurrently
-(``tfmpc_tvlqr_solve_time_parallel_f64``; double only, no gradients).
+(``tfmpc_tvlqr_solve_time_parallel_f64``; double only).  Their gradients are opt-in as the double
+solve's: ``differentiable=True`` saves the forward's gains and value function and differentiates through the segmented
+adjoint (``tfmpc_tvlqr_vjp_time_parallel_f64``), which repeats no Riccati step.
 """
 
 import numpy as np
@@ -400,19 +402,65 @@ class TimeVaryingLQR:
             return 1
         return segments
 
-    def solve_time_parallel(self, x0, segments=None, want_policy=False, want_value=False):
+    def default_vjp_segments(self, batch_size=None):
+        """The ``segments`` of the segmented adjoint (``tfmpc_tvlqr_vjp_time_parallel_f64``) where the forward's were not
+        given, fitted to profiles/tvlqr_time_parallel_grad_rate.json as :meth:`default_segments` was.  In
+        units of one step of the sequential VJP (25.5 us) a step of a segment costs 0.45 (condense and both expands), a
+        segment 0.22 (its two matrix-vector products in the serial stitches) and the call 4 (its launches), so the time is
+        ``0.45 ceil(T / P) + 0.22 P + 4``, least at ``P = sqrt(2.1 T)``: more, shorter segments than the forward's, whose
+        boundaries cost ten times as much.  The optimum did not move with the batch and the sequential VJP did not win
+        again at any measured batch (B <= 4096 at T = 512: it repeats the factorisation, this call does not), so there is
+        no cap in ``batch_size``; the answer is 1 -- ``tfmpc_tvlqr_vjp_f64`` -- where the model's time is not below ``T``."""
+        T = self.horizon
+        segments = min(int(round((2.1 * T) ** 0.5)), T)
+        if segments < 2 or 0.45 * -(-T // segments) + 0.22 * segments + 4 >= T:
+            return 1
+        return segments
+
+    def solve_time_parallel(self, x0, segments=None, want_policy=False, want_value=False, differentiable=False):
         """The solve with the horizon cut into ``segments`` pieces that are condensed, stitched and expanded concurrently
         (DESIGN.md 3.19): for a few long horizons, where one wavefront per instance leaves the device idle.  A
         :class:`Trajectory`; with ``want_policy`` / ``want_value`` a tuple ``(trajectory, K, k)``, ``(trajectory, V, v)`` or
         ``(trajectory, K, k, V, v)`` of device tensors (no ``const``: the value function's constant term is not carried
         across segments).  ``segments=None`` picks :meth:`default_segments`; a value above the horizon is clamped, 1 is the
-        sequential solve, bit for bit.  ``last_status`` is set as in :meth:`solve_device`.  Double precision only, no
-        gradients: use ``solve(x0, differentiable=True)`` for those."""
+        sequential solve, bit for bit.  ``last_status`` is set as in :meth:`solve_device`.  Double precision only.
+
+        Gradients are opt-in: with ``differentiable=True``, autograd recording and an operand or ``x0`` requiring grad, the
+        result is a :class:`~tfmpc.solvers.tvlqr_grad.TensorTrajectory` in the autograd graph (``K, k, V, v`` stay plain
+        tensors) whose backward is the segmented adjoint (``tfmpc_tvlqr_vjp_time_parallel_f64``) with the
+        forward's ``segments`` (:meth:`default_vjp_segments` where none were given); every gradient is fp64 and has its
+        operand's shape, and ``last_grad_status`` gets the backward's status.  Without the flag that request raises
+        ``NotImplementedError``; ``solve(x0, differentiable=True)`` is the sequential alternative."""
+        if differentiable and self.dtype == torch.float64 and tvlqr_grad.wants_grad(*self._sources, x0):
+            states, actions, costs, out = self._time_parallel_tensors(x0, segments)
+            fields = (("K", "k") if want_policy else ()) + (("V", "v") if want_value else ())
+            more = [out[name] if out["batched"] else out[name][0] for name in fields]
+            traj = tvlqr_grad.TensorTrajectory(states, actions, costs)
+            return (traj, *more) if more else traj
         out = self._time_parallel_device(x0, segments, want_policy, want_value)
         fields = ("states", "actions", "costs") + (("K", "k") if want_policy else ()) + (("V", "v") if want_value else ())
         tensors = [out[name] if out["batched"] else out[name][0] for name in fields]
         traj = trajectory.Trajectory(*tensors[:3])
         return (traj, *tensors[3:]) if tensors[3:] else traj
+
+    def _time_parallel_tensors(self, x0, segments=None):
+        """``(states, actions, costs, out)``: the time-parallel solve in the autograd graph of the caller's operands and
+        ``x0`` (``SolveTimeParallelFunctionF64``; without the batch axis for an un-batched problem), and the forward's device
+        dict (``K, k, V, v, batched, segments``: plain batched tensors)."""
+        if segments is not None and int(segments) < 1:
+            raise ValueError(f"segments must be at least 1, got {segments}")
+        out = {}
+
+        def run(x):
+            out.update(self._time_parallel_device(x, segments, True, True))
+            return out
+        given = segments is not None
+        problem = tvlqr_grad.Problem(run, lambda: self, True, self,
+                                     lambda B, used: used if given else self.default_vjp_segments(B))
+        states, actions, costs = tvlqr_grad.SolveTimeParallelFunctionF64.apply(problem, *self._graph_operands(x0))
+        if not out["batched"]:
+            states, actions, costs = states[0], actions[0], costs[0]
+        return states, actions, costs, out
 
     def _time_parallel_device(self, x0, segments=None, want_policy=False, want_value=False):
         """One tfmpc_tvlqr_solve_time_parallel_f64 call; a dict of batched device tensors as :meth:`solve_device`'s (no
@@ -421,8 +469,9 @@ class TimeVaryingLQR:
             raise NotImplementedError("the time-parallel solve is served in double only: build the problem with "
                                       "dtype=torch.float64")
         if tvlqr_grad.wants_grad(*self._sources, x0):
-            raise NotImplementedError("the time-parallel solve has no gradients (the double VJP's adjoint solve is serial in "
-                                      "the horizon): use solve(x0, differentiable=True), or detach the operands and x0")
+            raise NotImplementedError("gradients of the time-parallel solve are opt-in: pass differentiable=True to "
+                                      "solve_time_parallel / tvlqr_solve_time_parallel for the segmented adjoint, use "
+                                      "solve(x0, differentiable=True) for the sequential one, or detach the operands and x0")
         if segments is not None and int(segments) < 1:
             raise ValueError(f"segments must be at least 1, got {segments}")
         lib = _hip.require_gpu()
@@ -472,6 +521,26 @@ class TimeVaryingLQR:
             states, actions, costs = states[0], actions[0], costs[0]
         return trajectory.Trajectory(states, actions, costs)
 
+    def _graph_operands(self, x0):
+        """``(x0, F, f, C, c, C_final, c_final)`` as the differentiable Functions take them: the caller's tensors converted
+        inside the autograd graph and shaped as the solver holds them."""
+        n, d = self.state_size, self.n_dim
+        dev = self.device
+        src = self._sources
+
+        def op(i, own, shape=None):       # a non-tensor operand needs no grad: the solver's own copy, already shaped
+            if src[i] is None:
+                return own
+            t = tvlqr_grad.as_graph(src[i], dev, self.dtype)
+            return shape(t) if shape else t
+        F, C = op(0, self.F), op(2, self.C)
+        f = op(1, self.f, lambda t: self._vector(t, n, "f"))
+        c = op(3, self.c, lambda t: self._vector(t, d, "c"))
+        Cf = op(4, self.C_final)
+        cf = op(5, self.c_final, lambda t: t.unsqueeze(-1) if t.dim() == 1 or (t.dim() == 2 and t.shape != (n, 1)) else t)
+        x0g = _as_column(tvlqr_grad.as_graph(x0, dev, self.dtype), n)
+        return x0g, F, f, C, c, Cf, cf
+
     def solve_tensors(self, x0, differentiable=False):
         """``(states[(B,)T+1,n,1], actions[(B,)T,m,1], costs[(B,)T+1,1,1])`` as tensors; in the autograd graph of the
         caller's operands and ``x0`` when autograd is recording (gradients: tfmpc/solvers/tvlqr_grad.py).  With
@@ -484,39 +553,28 @@ class TimeVaryingLQR:
             out = self.solve_device(x0)
             states, actions, costs = out["states"], out["actions"], out["costs"]
         else:
-            n, d = self.state_size, self.n_dim
-            dev = self.device
-            src = self._sources
-
-            def op(i, own, shape=None):       # a non-tensor operand needs no grad: the solver's own copy, already shaped
-                if src[i] is None:
-                    return own
-                t = tvlqr_grad.as_graph(src[i], dev, self.dtype)
-                return shape(t) if shape else t
-            F, C = op(0, self.F), op(2, self.C)
-            f = op(1, self.f, lambda t: self._vector(t, n, "f"))
-            c = op(3, self.c, lambda t: self._vector(t, d, "c"))
-            Cf = op(4, self.C_final)
-            cf = op(5, self.c_final, lambda t: t.unsqueeze(-1) if t.dim() == 1 or (t.dim() == 2 and t.shape != (n, 1)) else t)
-            x0g = _as_column(tvlqr_grad.as_graph(x0, dev, self.dtype), n)
             problem = tvlqr_grad.Problem(lambda x: self.solve_device(x, want_v=double), lambda: self, True, self)
             function = tvlqr_grad.SolveFunctionF64 if double else tvlqr_grad.SolveFunction
-            states, actions, costs = function.apply(problem, x0g, F, f, C, c, Cf, cf)
+            states, actions, costs = function.apply(problem, *self._graph_operands(x0))
         if self._resolve_batch(self._prep_x0(x0.detach() if isinstance(x0, torch.Tensor) else x0)) is None:
             states, actions, costs = states[0], actions[0], costs[0]
         return states, actions, costs
 
 
-def tvlqr_solve_time_parallel(F, f, C, c, x0, segments=None, C_final=None, c_final=None):
+def tvlqr_solve_time_parallel(F, f, C, c, x0, segments=None, C_final=None, c_final=None, differentiable=False):
     """The time-parallel double-precision solve of :meth:`TimeVaryingLQR.solve_time_parallel` on operands in
     :class:`TimeVaryingLQR`'s shapes: ``(states, actions, costs)`` as float64 device tensors -- ``states[(B,)T+1,n,1]``,
     ``actions[(B,)T,m,1]``, ``costs[(B,)T+1,1,1]``.  ``F`` must be float64 (tensor or numpy): an fp32 problem raises
-    ``NotImplementedError``, as does an operand or ``x0`` that requires grad."""
+    ``NotImplementedError``, as does an operand or ``x0`` that requires grad -- unless ``differentiable=True``: the three
+    tensors are then in the autograd graph of every tensor operand and ``x0`` that requires grad, with fp64 gradients from
+    the segmented adjoint (``tfmpc_tvlqr_vjp_time_parallel_f64``)."""
     kind = F.dtype if isinstance(F, torch.Tensor) else np.asarray(F).dtype
     if kind not in (torch.float64, np.float64):
         raise NotImplementedError(f"the time-parallel solve is served in double only (dtype=torch.float64), F is {kind}")
     device = next((t.device for t in (F, f, C, c, x0) if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
     tv = TimeVaryingLQR(F, f, C, c, C_final, c_final, device=device, dtype=torch.float64)
+    if differentiable and tvlqr_grad.wants_grad(*tv._sources, x0):
+        return tv._time_parallel_tensors(x0, segments)[:3]
     out = tv._time_parallel_device(x0, segments)
     states, actions, costs = out["states"], out["actions"], out["costs"]
     return (states, actions, costs) if out["batched"] else (states[0], actions[0], costs[0])

@@ -1,6 +1,9 @@
 """Differentiable LQR solves: a ``torch.autograd.Function`` over ``tfmpc_tvlqr_solve_f32`` (or ``LQR``'s own solve) and
 ``tfmpc_tvlqr_vjp_f32`` (include/tfmpc_hip.h), and its double-precision twin over
-``tfmpc_tvlqr_solve_f64`` and ``tfmpc_tvlqr_vjp_f64``, which also saves the forward's ``v``.
+``tfmpc_tvlqr_solve_f64`` and ``tfmpc_tvlqr_vjp_f64``, which also saves the forward's ``v``.  A third
+Function stands over the time-parallel double solve and its segmented adjoint (``tfmpc_tvlqr_solve_time_parallel_f64``,
+``tfmpc_tvlqr_vjp_time_parallel_f64``): it saves the forward's ``K, V, v`` too, and its backward
+repeats no Riccati step.
 
 The backward pass is one more time-varying LQR solve (the adjoint) plus a costate sweep; it needs the forward
 trajectory only, which is what the Function saves.  Each gradient has the shape of its operand: an operand without a
@@ -42,10 +45,11 @@ def as_f32_graph(a, device):
 class Problem:
     """What the Function needs besides tensors: ``run(x0)`` -> the forward's ``solve_device`` dict (batched outputs),
     ``model()`` -> the :class:`TimeVaryingLQR` whose ``_model_args`` the VJP reads, ``timed`` (operands carry a time
-    axis) and ``owner`` (receives ``last_grad_status``)."""
+    axis) and ``owner`` (receives ``last_grad_status``); for the time-parallel solve also ``vjp_segments(B, segments)`` ->
+    the backward's segment count from the forward's."""
 
-    def __init__(self, run, model, timed, owner):
-        self.run, self.model, self.timed, self.owner = run, model, timed, owner
+    def __init__(self, run, model, timed, owner, vjp_segments=None):
+        self.run, self.model, self.timed, self.owner, self.vjp_segments = run, model, timed, owner, vjp_segments
 
 
 def grad_strides(g, ndim_batched, timed):
@@ -150,6 +154,57 @@ class SolveFunctionF64(torch.autograd.Function):
         return (None, gx0, gF, gf, gC, gc, gCf, gcf)
 
 
+def vjp_time_parallel_f64(tv, states, actions, K, V, v, ups, grads, segments):
+    """One ``tfmpc_tvlqr_vjp_time_parallel_f64`` call on the model of ``tv``: the forward's batched
+    ``states, actions, K, V, v``, the upstream gradients ``ups`` (three fp64 tensors or ``None``), the gradient buffers
+    ``grads = (gF, gf, gC, gc, gCf, gcf, gx0)`` (``None``: not computed; a missing batch or time axis sums over it).
+    Returns the per-instance status.  Never synchronises."""
+    lib = _hip.require_gpu()
+    Bk, T1, n = states.shape[0], states.shape[1], states.shape[2]
+    T, m = T1 - 1, actions.shape[2]
+    args = []
+    for g in grads[:4]:
+        args += [_hip.ptr(g), *grad_strides(g, 4, True)]
+    for g in grads[4:]:
+        args += [_hip.ptr(g), grad_strides(g, 3, False)[0]]
+    status = torch.zeros((Bk,), dtype=torch.int32, device=states.device)
+    ws_bytes = int(lib.tfmpc_tvlqr_vjp_time_parallel_workspace_bytes_f64(Bk, n, m, T, segments))
+    ws = torch.empty((max(ws_bytes, 8) + 7) // 8, dtype=torch.float64, device=states.device)
+    rc = lib.tfmpc_tvlqr_vjp_time_parallel_f64(Bk, n, m, T, *tv._model_args(), _hip.ptr(states), _hip.ptr(actions), _hip.ptr(v),
+                                               _hip.ptr(K), _hip.ptr(V), *(_hip.ptr(u) for u in ups), *args, _hip.ptr(status),
+                                               segments, _hip.ptr(ws), ws.numel() * 8, _hip.stream())
+    _hip.check(rc, "tfmpc_tvlqr_vjp_time_parallel_f64")
+    return status
+
+
+class SolveTimeParallelFunctionF64(torch.autograd.Function):
+    """``SolveFunctionF64`` over the time-parallel solve: the forward asks it for ``K, k, V, v``
+    (``problem.run`` returns them and the resolved ``segments``) and saves ``states, actions, K, V, v``; the backward calls
+    ``tfmpc_tvlqr_vjp_time_parallel_f64`` with ``problem.vjp_segments(B, segments)`` segments."""
+
+    @staticmethod
+    def forward(ctx, problem, x0, F, f, C, c, C_final, c_final):
+        out = problem.run(x0.detach())
+        ctx.problem = problem
+        ctx.segments = out["segments"]
+        ctx.meta = [(t.shape if t is not None else None) for t in (x0, F, f, C, c, C_final, c_final)]
+        ctx.save_for_backward(out["states"], out["actions"], out["K"], out["V"], out["v"])
+        return out["states"], out["actions"], out["costs"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_states, g_actions, g_costs):
+        states, actions, K, V, v = ctx.saved_tensors
+        problem = ctx.problem
+        f64 = torch.float64
+        gx0, gF, gf, gC, gc, gCf, gcf = alloc_grads(ctx.meta, ctx.needs_input_grad[1:], states.shape[0], states.device, f64)
+        ups = [None if g is None else g.to(f64).contiguous() for g in (g_states, g_actions, g_costs)]
+        segments = problem.vjp_segments(states.shape[0], ctx.segments)
+        problem.owner.last_grad_status = vjp_time_parallel_f64(problem.model(), states, actions, K, V, v, ups,
+                                                               (gF, gf, gC, gc, gCf, gcf, gx0), segments)
+        return (None, gx0, gF, gf, gC, gc, gCf, gcf)
+
+
 class TensorTrajectory(trajectory.Trajectory):
     """The :class:`~tfmpc.utils.trajectory.Trajectory` a differentiable ``solve`` returns: the same shapes and
     properties, but ``states``, ``actions`` and ``costs`` stay torch tensors in the autograd graph."""
@@ -207,4 +262,42 @@ def tvlqr_solve(F, f, C, c, x0, C_final=None, c_final=None, dtype=torch.float32)
     return tv.solve_tensors(x0, differentiable=True)
 
 
-__all__ = ["SolveFunction", "SolveFunctionF64", "TensorTrajectory", "tvlqr_solve"]
+def tvlqr_vjp_time_parallel(F, f, C, c, states, actions, K, V, v, g_states=None, g_actions=None, g_costs=None, C_final=None,
+                            c_final=None, segments=None):
+    """The vector-Jacobian product of the double-precision solve alone through the segmented adjoint
+    (``tfmpc_tvlqr_vjp_time_parallel_f64``), for any forward: ``states, actions, K, V, v`` as a solve of
+    ``(F, f, C, c, C_final, c_final)`` gave them (batched; operands that all lack the batch axis are shared by the
+    trajectories' batch), ``g_states, g_actions, g_costs`` the upstream gradients (``None`` = zero).  ``segments=None`` picks
+    :meth:`TimeVaryingLQR.default_vjp_segments`; 1 is ``tfmpc_tvlqr_vjp_f64``, bit for bit.  Returns ``(dF, df, dC, dc,
+    dC_final, dc_final, dx0, status)``: each gradient float64 in its operand's shape as :class:`TimeVaryingLQR` holds it
+    (vectors as columns; an operand without a batch axis gets the sum over the batch, a time axis of 1 the sum over time;
+    ``None`` for an absent final cost, whose gradient is then in ``dC, dc`` at the last step; ``dx0`` is ``[(B,) n, 1]``)
+    and the per-instance status; a flagged instance has NaN in its own gradient rows and in every sum that contains it."""
+    from tfmpc.solvers.tvlqr import TimeVaryingLQR, _as_dtype
+    f64 = torch.float64
+    tensors = (F, f, C, c, C_final, c_final, states)
+    device = next((t.device for t in tensors if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
+    tv = TimeVaryingLQR(F, f, C, c, C_final, c_final, device=device, dtype=f64)
+    dev = tv.device
+    n, m, T = tv.state_size, tv.action_size, tv.horizon
+    states, actions, K, V, v = (_as_dtype(t, dev, f64).reshape(-1, steps, *inner).contiguous()
+                                for t, steps, inner in ((states, T + 1, (n, 1)), (actions, T, (m, 1)), (K, T, (m, n)),
+                                                        (V, T, (n, n)), (v, T, (n, 1))))
+    Bk = tv.batch_size if tv.batch_size is not None else states.shape[0]      # a model shared by a batch of trajectories
+    if any(t.shape[0] != Bk for t in (states, actions, K, V, v)):
+        raise ValueError("states, actions, K, V and v must share the operands' batch size")
+    ups = [None if g is None else _as_dtype(g, dev, f64).reshape(Bk, steps, *inner).contiguous()
+           for g, steps, inner in ((g_states, T + 1, (n, 1)), (g_actions, T, (m, 1)), (g_costs, T + 1, (1, 1)))]
+    shapes = [(t.shape if t is not None else None) for t in (tv.F, tv.f, tv.C, tv.c, tv.C_final, tv.c_final)]
+    shapes.append((Bk, n, 1) if tv.batch_size is not None or Bk > 1 else (n, 1))
+    grads = alloc_grads(shapes, (True,) * 7, Bk, dev, f64)
+    segments = tv.default_vjp_segments(Bk) if segments is None else int(segments)
+    if segments < 1:
+        raise ValueError(f"segments must be at least 1, got {segments}")
+    status = vjp_time_parallel_f64(tv, states, actions, K, V, v, ups, grads, segments)
+    tv.last_grad_status = status
+    return (*grads, status)
+
+
+__all__ = ["SolveFunction", "SolveFunctionF64", "SolveTimeParallelFunctionF64", "TensorTrajectory", "tvlqr_solve",
+           "tvlqr_vjp_time_parallel"]
