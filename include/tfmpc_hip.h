@@ -279,6 +279,44 @@ int tfmpc_tvlqr_solve_time_parallel_f64(int B, int n, int m, int T,
                                         double *K, double *k, double *V, double *v, double *cst, int32_t *status,
                                         int segments, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------- periodic infinite-horizon LQR, double precision --------
+ * The infinite-horizon problem whose model repeats with period N: F, f, C, c are ONE PERIOD, with
+ * tfmpc_tvlqr_solve_f64's operand layout and strides (0 allowed on either axis; a time stride of 0 with N > 1 is the
+ * stationary problem sampled N times); there is no final cost and no x0.  Outputs, each optional: the periodic stabilising
+ * gains K[B][N][m][n], k[B][N][m] and value function V[B][N][n][n], v[B][N][n], V[b][t], v[b][t] AT step t as
+ * tfmpc_tvlqr_backward_f64's (V[b][0] = P_0; V_N = V_0, v_N = v_0); residual[B] (optional): one more turn around the period
+ * from (P_0, p_0), max(max|V - P_0| / max|P_0|, max|v - p_0| / max(1, max|p_0|)), a self-check; iterations[B]
+ * (optional): doubling steps taken; status[B] (required).
+ * Four kernels on the caller's stream: the time-parallel solve's condense on the period's segments (`segments` clamped
+ * to N: len = ceil(N / segments), P = ceil(N / len)); a stitch, one wave per instance, that folds the P elements into
+ * the one-period element, doubles it -- the element of 2^k periods: H_k -> P_0, h_k -> p_0, A_k -> 0 -- until
+ * max|H_k - H_{k-1}| <= tol max|H_k|, max|h_k - h_{k-1}| <= tol max(1, max|h_k|) and max|A_k| <= 1e-3, certifies the
+ * closed-loop monodromy (I + G1 P_0)^-1 A1 by squaring it below 1e-3 within max_iter squarings, and carries (P_0, p_0)
+ * backwards over the seams; an expand, one wave per (instance, segment), that runs tfmpc_tvlqr_backward_f64's recursion
+ * on its segment; a finish that ORs the status words.  max_iter 0 -> 40, tol 0 -> 4 DBL_EPSILON.
+ * Checks: tfmpc_tvlqr_solve_time_parallel_f64's on the model, in its order (n > 32 or m > 32: TFMPC_ERR_UNSUPPORTED), then
+ * segments < 1, max_iter < 0 or tol < 0: TFMPC_ERR_ARG; B == 0 is a no-op; status == NULL, a workspace that is NULL,
+ * smaller than workspace_bytes or not 8-byte aligned: TFMPC_ERR_ARG.  The workspace is always required: with w = B P,
+ *   8 ((w + B) (3 n n + 2 n) + w (n n + n) + B N m (n + 1)) + the bytes of 2 w + B status words rounded up to 8
+ * (the segment and the one-period elements, the value behind every segment, the gains; 0 for an invalid argument).
+ * status[b]: TFMPC_ST_NOT_PD for a step's R_t or Q_uu not positive definite, TFMPC_ST_SINGULAR for a zero pivot in any
+ * I + G H, I + P G or I + G P, TFMPC_ST_NOT_STABILISING when the doubling meets a non-finite value or does not stop within
+ * max_iter steps or the certificate fails, TFMPC_ST_NAN as the sequential solve.  A phase does not run on an instance an
+ * earlier phase flagged, so the word names the cause.  A flagged instance has NaN in all its outputs (iterations keeps
+ * its count); no other instance is affected.  No atomics, no allocation, no sync: an instance's bits depend on neither B
+ * nor its position, and repeated calls give identical bits.  kernel_name: "tv_f64_periodic16" (n <= 16 and m <= 16) or
+ * "tv_f64_periodic32", "unsupported", "invalid".  TFMPC_TVLQR_TP_PHASES = 1 | 2 | 3 stops the call after its condense /
+ * stitch / expand launch (TFMPC_TVLQR_TP_STOPPED; timing only). */
+size_t tfmpc_tvlqr_periodic_workspace_bytes_f64(int B, int n, int m, int N, int segments);
+const char *tfmpc_tvlqr_periodic_kernel_name_f64(int n, int m, int N, int segments);
+int tfmpc_tvlqr_periodic_steady_state_f64(int B, int n, int m, int N,
+                                          const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                                          const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                                          int segments, int max_iter, double tol,
+                                          double *K, double *k, double *V, double *v, double *residual,
+                                          int32_t *iterations, int32_t *status,
+                                          void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------ TV-LQR gradients --------
  * Vector-Jacobian product of tfmpc_tvlqr_solve_f32: given the forward's states[B][T+1][n] (states[b][0]
  * is x0) and actions[B][T][m], and upstream gradients g_states[B][T+1][n], g_actions[B][T][m], g_costs[B][T+1] (each

@@ -3,6 +3,7 @@
 // checks in the same order; only the support test and the launcher differ.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdint>
 
 #include "lqr_kernels.h"
@@ -141,6 +142,19 @@ size_t time_parallel_workspace_bytes(int B, int n, int m, int T, int segments)
     return sizeof(double) * (w * (tv_tp_elem_doubles(n) + (size_t)n * n + 2 * n) + (size_t)B * T * m * (n + 1)) +
            up8(sizeof(int32_t) * (2 * w + B));
 }
+
+// doubles: the segment elements and the one-period elements, the value function at every segment's end, the gains; then
+// the status words
+size_t periodic_workspace_bytes(int B, int n, int m, int N, int segments)
+{
+    if (B <= 0 || n <= 0 || m <= 0 || N <= 0 || segments < 1) return 0;
+    const size_t w = (size_t)B * segment_table(N, segments).count;
+    return sizeof(double) * ((w + B) * tv_tp_elem_doubles(n) + w * ((size_t)n * n + n) + (size_t)B * N * m * (n + 1)) +
+           up8(sizeof(int32_t) * (2 * w + B));
+}
+
+constexpr int kPeriodicMaxIter = 40;                     // DESIGN.md 3.16's defaults
+constexpr double kPeriodicTol = 4.0 * DBL_EPSILON;
 
 }  // namespace
 
@@ -306,6 +320,75 @@ int tfmpc_tvlqr_solve_time_parallel_f64(TFMPC_TVLQR_MODEL_PARAMS(double), const 
     if (!K) a.K = nullptr;                                   // scratch gains are nobody's output
     if (!k) a.k = nullptr;
     return tvlqr_time_parallel_f64_finish_launch(a, tp, s);
+}
+
+size_t tfmpc_tvlqr_periodic_workspace_bytes_f64(int B, int n, int m, int N, int segments)
+{
+    return periodic_workspace_bytes(B, n, m, N, segments);
+}
+
+const char *tfmpc_tvlqr_periodic_kernel_name_f64(int n, int m, int N, int segments)
+{
+    if (n <= 0 || m <= 0 || N <= 0 || segments < 1) return "invalid";
+    if (!supported(double(), n, m)) return "unsupported";
+    return tvlqr_periodic_f64_kernel_name(n, m);
+}
+
+int tfmpc_tvlqr_periodic_steady_state_f64(int B, int n, int m, int N, const double *F, long sF_b, long sF_t,
+                                          const double *f, long sf_b, long sf_t, const double *C, long sC_b, long sC_t,
+                                          const double *c, long sc_b, long sc_t, int segments, int max_iter, double tol,
+                                          double *K, double *k, double *V, double *v, double *residual,
+                                          int32_t *iterations, int32_t *status, void *workspace, size_t workspace_bytes,
+                                          void *stream)
+{
+    const Model<double> md{F, sF_b, sF_t, f, sf_b, sf_t, C, sC_b, sC_t, c, sc_b, sc_t, nullptr, 0, nullptr, 0};
+    int rc = check_model(B, n, m, N, md);
+    if (rc != TFMPC_OK) return rc;
+    if (segments < 1 || max_iter < 0 || !(tol >= 0.0)) return TFMPC_ERR_ARG;
+    if (B == 0) return TFMPC_OK;
+    if (!status) return TFMPC_ERR_ARG;
+    const SegmentTable tab = segment_table(N, segments);
+    const size_t waves = (size_t)B * tab.count;
+    if (waves > (size_t)INT32_MAX) return TFMPC_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < periodic_workspace_bytes(B, n, m, N, segments)) return TFMPC_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(workspace) % sizeof(double)) return TFMPC_ERR_ARG;      // doubles are carved from it
+    TvTimeParallel tp{};
+    tp.segments = tab.count;
+    tp.len = tab.len;
+    TvPeriodic pp{};
+    pp.max_iter = max_iter ? max_iter : kPeriodicMaxIter;
+    pp.tol = tol > 0.0 ? tol : kPeriodicTol;
+    pp.residual = residual;
+    pp.iterations = iterations;
+    double *w = static_cast<double *>(workspace);
+    tp.elems = w; w += waves * tv_tp_elem_doubles(n);
+    pp.E1 = w; w += (size_t)B * tv_tp_elem_doubles(n);
+    tp.Vend = w; w += waves * n * n;
+    tp.vend = w; w += waves * n;
+    double *gains = w; w += (size_t)B * N * m * (n + 1);
+    int32_t *st = reinterpret_cast<int32_t *>(w);
+    tp.st_condense = st;
+    tp.st_expand = st + waves;
+    tp.st_stitch = st + 2 * waves;
+    TvLqrArgsT<double> a = make_args(B, n, m, N, md);
+    a.K = K ? K : gains;
+    a.k = k ? k : gains + (size_t)B * N * m * n;
+    a.sK = (long)N * m * n; a.sk = (long)N * m;
+    a.V = V; a.v = v;
+    a.status = status;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // TFMPC_TVLQR_TP_PHASES=1|2|3: stop after the condense / the stitch / the expand launch, as the time-parallel solve
+    // does -- for the phase split of tools/tvlqr_periodic_rate.py only: TFMPC_TVLQR_TP_STOPPED, not OK
+    const int phases = option_int(kOptTvlqrTpPhases, 4);
+    if ((rc = tvlqr_time_parallel_f64_condense_launch(a, tp, s)) != TFMPC_OK) return rc;
+    if (phases == 1) return TFMPC_TVLQR_TP_STOPPED;
+    if ((rc = tvlqr_periodic_f64_stitch_launch(a, tp, pp, s)) != TFMPC_OK) return rc;
+    if (phases == 2) return TFMPC_TVLQR_TP_STOPPED;
+    if ((rc = tvlqr_f64_periodic_expand_launch(a, tp, s)) != TFMPC_OK) return rc;
+    if (phases == 3) return TFMPC_TVLQR_TP_STOPPED;
+    if (!K) a.K = nullptr;                                   // scratch gains are nobody's output
+    if (!k) a.k = nullptr;
+    return tvlqr_periodic_f64_finish_launch(a, tp, pp, s);
 }
 
 }  // extern "C"

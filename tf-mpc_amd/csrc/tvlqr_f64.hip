@@ -2,8 +2,8 @@
 // n <= 32 and m <= 32.
 //
 // The double instantiation of tvlqr_wave.h's body: products on v_mfma_f64_16x16x4_f64 (wave_ops_f64.h), the folded LDS
-// layout.  Also the expand kernel of the time-parallel solve: the same body on one segment of the
-// horizon.  The entry points are in tvlqr_dispatch.hip.
+// layout.  Also the expand kernels of the time-parallel solve and of the periodic steady state (3.25):
+// the same body on one segment of the horizon / of the period.  The entry points are in tvlqr_dispatch.hip.
 #include <hip/hip_runtime.h>
 
 #include "tvlqr_wave.h"
@@ -69,6 +69,41 @@ int expand_for(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_
     return launch_with_lds(tvlqr_expand_f64_kernel<MAXD>, (unsigned)a.B * tp.segments, kWave, smem, stream, a, tp);
 }
 
+// The expand phase of the periodic steady state: the body's backward sweep alone on segment i of the
+// period, from the value function the periodic stitch left behind the segment; no rollout, no final cost.  The waves
+// of an instance that condense or stitch flagged do not run (the finish kernel fills its outputs).
+template <int MAXD>
+__global__ __launch_bounds__(kWave) void tvlqr_periodic_expand_f64_kernel(TvLqrArgsT<double> a, TvTimeParallel tp)
+{
+    extern __shared__ double smem_f64[];
+    const size_t w = blockIdx.x;
+    const int n = a.n, lane = lane_id();
+    TvSegment<double> seg;
+    seg.b = (int)(blockIdx.x / (unsigned)tp.segments);
+    const int i = (int)blockIdx.x - seg.b * tp.segments;
+    int flagged = lane == 0 ? tp.st_stitch[seg.b] : 0;
+    for (int s = lane; s < tp.segments; s += kWave) flagged |= tp.st_condense[(size_t)seg.b * tp.segments + s];
+    if (__ballot(flagged != 0)) {
+        if (lane == 0) tp.st_expand[w] = 0;
+        return;
+    }
+    seg.t0 = i * tp.len;
+    seg.len = a.T - seg.t0 < tp.len ? a.T - seg.t0 : tp.len;
+    seg.last = false;
+    seg.Vend = tp.Vend + w * n * n;
+    seg.vend = tp.vend + w * n;
+    seg.xstart = nullptr;
+    seg.status = tp.st_expand + w;
+    tvlqr_wave_body<TvF64<MAXD>, true, false, false, TvSegment<double>>(a, smem_f64, seg);
+}
+
+template <int MAXD>
+int periodic_expand_for(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream)
+{
+    const size_t smem = tv_smem_elems<true>(a.n, a.m) * sizeof(double);
+    return launch_with_lds(tvlqr_periodic_expand_f64_kernel<MAXD>, (unsigned)a.B * tp.segments, kWave, smem, stream, a, tp);
+}
+
 // The masked sweep (tvlqr_solve_masked_f64): the body with the held controls taken out of each step's
 // model; FORWARD = false is the backward sweep alone, for a caller that wants the value function only.
 template <int MAXD, bool FORWARD>
@@ -107,6 +142,11 @@ int tvlqr_f64_masked_launch(const TvLqrArgsT<double> &a, bool forward, hipStream
 int tvlqr_f64_expand_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream)
 {
     return wave16(a.n, a.m) ? expand_for<16>(a, tp, stream) : expand_for<32>(a, tp, stream);
+}
+
+int tvlqr_f64_periodic_expand_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream)
+{
+    return wave16(a.n, a.m) ? periodic_expand_for<16>(a, tp, stream) : periodic_expand_for<32>(a, tp, stream);
 }
 
 }  // namespace tfmpc

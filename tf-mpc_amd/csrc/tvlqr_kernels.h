@@ -66,6 +66,26 @@ int tvlqr_time_parallel_f64_stitch_launch(const TvLqrArgsT<double> &a, const TvT
 int tvlqr_f64_expand_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream);
 int tvlqr_time_parallel_f64_finish_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream);
 
+// The periodic infinite-horizon LQR in double (tfmpc_tvlqr_periodic_steady_state_f64): a.T is ONE PERIOD,
+// cut into tp.segments pieces as the time-parallel solve cuts a horizon (tp.xstart is not used); a.Cfin, a.x0 and the
+// rollout's outputs are NULL.
+struct TvPeriodic {
+    int max_iter;
+    double tol;
+    double *E1;                   // [B][3 n n + 2 n]: the one-period element
+    double *residual;             // [B] or NULL
+    int32_t *iterations;          // [B] or NULL
+};
+const char *tvlqr_periodic_f64_kernel_name(int n, int m);
+// condense (the time-parallel solve's own launch), periodic stitch (tvlqr_periodic_f64.hip), expand without a rollout
+// (tvlqr_f64.hip; a.K and a.k are written, the caller's or scratch), then the status OR and the NaN fill of flagged
+// instances (every non-NULL of a.K, a.k, a.V, a.v and pp.residual; a.status is required)
+int tvlqr_periodic_f64_stitch_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, const TvPeriodic &pp,
+                                     hipStream_t stream);
+int tvlqr_f64_periodic_expand_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, hipStream_t stream);
+int tvlqr_periodic_f64_finish_launch(const TvLqrArgsT<double> &a, const TvTimeParallel &tp, const TvPeriodic &pp,
+                                     hipStream_t stream);
+
 // tfmpc_tvlqr_solve_f32 (same arguments, K = k = V = v = cst = NULL) on a MASKED model: for every set bit i of
 // mask[b][t], column n + i of F_t is read as zero, row and column n + i of C_t as zero with a unit diagonal, and
 // entry n + i of c_t as zero, so that row i of K_t and k_t[i] are exactly zero.  The mask is applied as the operands

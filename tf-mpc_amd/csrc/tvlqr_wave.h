@@ -1,6 +1,7 @@
 // tvlqr_wave.h -- the ONE body of the wave-per-instance time-varying LQR: LDS layout, backward
 // sweep, rollout and launcher, instantiated in fp32 by tvlqr_generic.hip and in double by tvlqr_f64.hip (whole horizons,
-// and single segments for the time-parallel solve's expand phase).
+// and single segments for the expand phases of the time-parallel solve, DESIGN.md 3.19, and of the periodic steady
+// state, 3.25: there the backward sweep alone).
 //
 // Per step t of the backward sweep the wave copies F_t, f_t, C_t, c_t into its LDS slice and runs the symmetric
 // recursion of the fast kernels: W = F_t^T V, Q = C_t + W F_t and V' = Q_xx + Q_xu K on the matrix cores, q = c_t + W f_t

@@ -19,7 +19,7 @@ ERRORS = {-1: "bad argument", -2: "shape not supported by any kernel variant",
           1: "stopped after a phase on request (TFMPC_TVLQR_TP_PHASES is set): no output was written"}
 
 ST_SINGULAR, ST_NOT_PD, ST_NAN, ST_QP_MAXITER, ST_MAX_ATTEMPTS, ST_QP_LATER_NOT_PD, ST_ENV_FLAG = 1, 2, 4, 8, 16, 32, 64
-ST_NOT_STABILISING = 128      # tfmpc_lqr_steady_state_f32: no stabilising solution found
+ST_NOT_STABILISING = 128      # tfmpc_lqr_steady_state_*, tfmpc_tvlqr_periodic_steady_state_f64: no stabilising solution found
 
 _P, _I, _L, _Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t
 
@@ -61,6 +61,12 @@ _SIGNATURES.update({
     "tfmpc_tvlqr_time_parallel_workspace_bytes_f64": (_Z, [_I, _I, _I, _I, _I]),
     "tfmpc_tvlqr_time_parallel_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I, _I]),
     "tfmpc_tvlqr_solve_time_parallel_f64": (_I, _TV_MODEL + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    # the periodic infinite-horizon LQR in double: B n m N, F f C c (+ batch, time strides), segments
+    # max_iter tol, K k V v residual, iterations status, workspace workspace_bytes stream
+    "tfmpc_tvlqr_periodic_workspace_bytes_f64": (_Z, [_I, _I, _I, _I, _I]),
+    "tfmpc_tvlqr_periodic_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I, _I]),
+    "tfmpc_tvlqr_periodic_steady_state_f64": (_I, [_I, _I, _I, _I] + [_P, _L, _L] * 4 + [_I, _I, ctypes.c_double] + [_P] * 7
+                                              + [_P, _Z, _P]),
     "tfmpc_tvlqr_vjp_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     # states actions, g_states g_actions g_costs, dF df dC dc (+ batch, time strides), dCfin dcfin dx0 (+ batch stride)
     "tfmpc_tvlqr_vjp_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3 + [_P, _P, _Z, _P]),

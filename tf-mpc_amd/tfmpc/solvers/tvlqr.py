@@ -21,7 +21,14 @@ A few long horizons (B <= 64 or so, T in the hundreds or thousands): ``solve_tim
 (``tfmpc_tvlqr_solve_time_parallel_f64``; double only).  Their gradients are opt-in as the double
 solve's: ``differentiable=True`` saves the forward's gains and value function and differentiates through the segmented
 adjoint (``tfmpc_tvlqr_vjp_time_parallel_f64``), which repeats no Riccati step.
+
+A model that REPEATS with period N, over an infinite horizon: ``periodic_steady_state`` /
+:func:`tvlqr_periodic_steady_state` take the time axis as one period and return the stationary cycle of gains and value
+functions with a per-instance status (``tfmpc_tvlqr_periodic_steady_state_f64``; double only, no
+gradients yet).
 """
+
+import collections
 
 import numpy as np
 import torch
@@ -33,6 +40,10 @@ from tfmpc.utils import trajectory
 
 
 _DTYPES = (torch.float32, torch.float64)
+
+# The periodic stationary solution: K[(B,)N,m,n], k[(B,)N,m,1], V[(B,)N,n,n], v[(B,)N,n,1] -- V[t], v[t] the
+# value function AT step t of the period, so V[0] = P_0 and V_N = V_0 -- residual[(B)], iterations[(B)], status[(B)]
+PeriodicSteadyState = collections.namedtuple("PeriodicSteadyState", "K k V v residual iterations status")
 
 
 def _check_dtype(dtype):
@@ -309,6 +320,8 @@ class TimeVaryingLQR:
         x0 = self._prep_x0(x0)
         if isinstance(policy, Policy):
             K, k = policy.K, policy.k
+        elif isinstance(policy, tuple) and len(policy) == 2 and all(isinstance(t, torch.Tensor) and t.dim() >= 3 for t in policy):
+            K, k = policy                   # (K[(B,)T,m,n], k[(B,)T,m,1]) as stacked tensors
         else:
             tdim = self._cast(policy[0][0]).dim() - 2
             K = torch.stack([self._cast(p[0]) for p in policy], dim=tdim)
@@ -505,6 +518,63 @@ class TimeVaryingLQR:
         out.update(batched=B is not None, segments=segments, workspace=workspace)
         return out
 
+    # -- the model as one period of an infinite horizon (tfmpc_tvlqr_periodic_steady_state_f64) -----
+    def periodic_steady_state(self, segments=None, max_iter=0, tol=0.0):
+        """The model's time axis taken as ONE PERIOD of an infinite-horizon problem whose model repeats: the stationary
+        cycle of gains and value functions, a :class:`PeriodicSteadyState` of float64 device tensors ``K[(B,)N,m,n]``,
+        ``k[(B,)N,m,1]``, ``V[(B,)N,n,n]``, ``v[(B,)N,n,1]`` (``V[t], v[t]`` AT step t: ``V[0]`` is the value function at
+        phase 0, and ``V_N = V_0``), ``residual[(B)]`` (one more turn around the period from ``V[0], v[0]``, relative: a
+        self-check), ``iterations[(B)]`` (doubling steps) and ``status[(B)]`` (0, or ``TFMPC_ST_NOT_PD`` / ``_SINGULAR`` /
+        ``_NOT_STABILISING`` / ``_NAN``; a flagged instance has NaN in its outputs).  ``last_status`` is set.  One period is
+        condensed into a segment element on ``segments`` concurrent waves (``None``: :meth:`default_segments`), the
+        element is doubled until it is stationary, and every segment is expanded.  ``max_iter=0`` is 40
+        doubling steps, ``tol=0`` is 4 ``DBL_EPSILON``.  Never synchronises.
+
+        The result composes with the finite solvers: ``forward((K, k), x0)`` rolls one period out, and
+        ``TimeVaryingLQR(F[:, :L], ..., C_final=V[:, L % N], c_final=v[:, L % N], dtype=torch.float64)`` is the finite
+        solve that ends at phase ``L`` of the cycle.
+
+        Double precision only (``NotImplementedError`` for an fp32 problem: build it with ``dtype=torch.float64``); the
+        periodic problem has no final cost (``ValueError`` if the problem carries ``C_final`` / ``c_final``); gradients
+        of the periodic solution are not implemented yet (``NotImplementedError`` if an operand requires grad)."""
+        if self.dtype != torch.float64:
+            raise NotImplementedError("the periodic steady state is served in double only: build the problem with "
+                                      "dtype=torch.float64")
+        if self.C_final is not None:
+            raise ValueError("the periodic infinite-horizon problem has no final cost: build the problem without "
+                             "C_final / c_final")
+        if tvlqr_grad.wants_grad(*self._sources):
+            raise NotImplementedError("gradients of the periodic steady state are not implemented yet (a follow-up, "
+                                      "DESIGN.md 3.25): detach the operands")
+        if segments is not None and int(segments) < 1:
+            raise ValueError(f"segments must be at least 1, got {segments}")
+        max_iter, tol = int(max_iter), float(tol)
+        if max_iter < 0 or not tol >= 0.0:
+            raise ValueError(f"max_iter and tol must not be negative, got {max_iter}, {tol}")
+        lib = _hip.require_gpu()
+        n, m, N = self.state_size, self.action_size, self.horizon
+        B = self.batch_size
+        Bk = B if B is not None else 1
+        segments = self.default_segments(Bk) if segments is None else int(segments)
+        dev, dt = self.device, self.dtype
+        K = torch.empty((Bk, N, m, n), device=dev, dtype=dt)
+        k = torch.empty((Bk, N, m, 1), device=dev, dtype=dt)
+        V = torch.empty((Bk, N, n, n), device=dev, dtype=dt)
+        v = torch.empty((Bk, N, n, 1), device=dev, dtype=dt)
+        residual = torch.empty((Bk,), device=dev, dtype=dt)
+        iterations = torch.empty((Bk,), dtype=torch.int32, device=dev)
+        status = (torch.zeros if Bk == 0 else torch.empty)((Bk,), dtype=torch.int32, device=dev)
+        ws_bytes = int(lib.tfmpc_tvlqr_periodic_workspace_bytes_f64(Bk, n, m, N, segments))
+        workspace = torch.empty(max(ws_bytes // 8, 1), dtype=dt, device=dev)
+        rc = lib.tfmpc_tvlqr_periodic_steady_state_f64(
+            Bk, n, m, N, *self._model_args()[:12], segments, max_iter, tol, _hip.ptr(K), _hip.ptr(k), _hip.ptr(V),
+            _hip.ptr(v), _hip.ptr(residual), _hip.ptr(iterations), _hip.ptr(status), _hip.ptr(workspace),
+            workspace.numel() * 8, _hip.stream())
+        _hip.check(rc, "tfmpc_tvlqr_periodic_steady_state_f64")
+        self.last_status = status
+        out = (K, k, V, v, residual, iterations, status)
+        return PeriodicSteadyState(*(out if B is not None else (t[0] for t in out)))
+
     def solve(self, x0, differentiable=False):
         """A :class:`Trajectory`; with autograd recording and an operand or ``x0`` requiring grad, a
         :class:`~tfmpc.solvers.tvlqr_grad.TensorTrajectory` differentiable through ``tfmpc_tvlqr_vjp_f32``.  With
@@ -580,4 +650,16 @@ def tvlqr_solve_time_parallel(F, f, C, c, x0, segments=None, C_final=None, c_fin
     return (states, actions, costs) if out["batched"] else (states[0], actions[0], costs[0])
 
 
-__all__ = ["TimeVaryingLQR", "tvlqr_solve_time_parallel"]
+def tvlqr_periodic_steady_state(F, f, C, c, segments=None, max_iter=0, tol=0.0):
+    """:meth:`TimeVaryingLQR.periodic_steady_state` on operands in :class:`TimeVaryingLQR`'s shapes, their time axis one
+    period: a :class:`PeriodicSteadyState`.  ``F`` must be float64 (tensor or numpy): an fp32 problem raises
+    ``NotImplementedError``, as does an operand that requires grad (gradients of the periodic solution are a follow-up)."""
+    kind = F.dtype if isinstance(F, torch.Tensor) else np.asarray(F).dtype
+    if kind not in (torch.float64, np.float64):
+        raise NotImplementedError(f"the periodic steady state is served in double only (dtype=torch.float64), F is {kind}")
+    device = next((t.device for t in (F, f, C, c) if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
+    tv = TimeVaryingLQR(F, f, C, c, device=device, dtype=torch.float64)
+    return tv.periodic_steady_state(segments, max_iter, tol)
+
+
+__all__ = ["TimeVaryingLQR", "PeriodicSteadyState", "tvlqr_solve_time_parallel", "tvlqr_periodic_steady_state"]
