@@ -455,6 +455,56 @@ int tfmpc_tvlqr_backward_vjp_f64(int B, int n, int m, int T,
                                  double *dCfin, long sdCfin_b, double *dcfin, long sdcfin_b,
                                  int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------- periodic infinite-horizon LQR gradients, double precision --------
+ * Vector-Jacobian product of tfmpc_tvlqr_periodic_steady_state_f64: given the model of ONE PERIOD with
+ * its strides as in the forward, the forward's K[B][N][m][n], k[B][N][m], V[B][N][n][n], v[B][N][n] and status
+ * (fwd_status[B], required) and upstream gradients gK, gk, gV, gv in the shapes of K, k, V, v (each optional, NULL = zero),
+ * the gradients dF[n][d], df[n], dC[d][d] (symmetric), dc[d] per (b, t), each optional, each with a batch and a time stride
+ * in elements as in tfmpc_tvlqr_backward_vjp_f64.  The step is that entry's with P = V[(t + 1) % N]; the period has no
+ * final cost, so the adjoint (X, y) of (V_0, v_0) that leaves step N - 1 re-enters step 0.  One lap maps it affinely and
+ * block-triangularly, y_out = Phi y + s_y, X_out = Phi X Phi' + L(y) + S_X with Phi the closed-loop monodromy, and the
+ * fixed point takes three sweeps of the period -- A from (0, 0), B from (0, y*), C from (X*, y*), which writes the
+ * gradients -- on one wave per (instance, segment) (`segments` clamped to N: len = ceil(N / segments), P = ceil(N / len)),
+ * and two stitches on one wave per instance: y* = (I - Phi)^-1 s_y by pivoted elimination, and X* = Phi X* Phi' + W by Smith
+ * doubling, X <- X + Phi_k X Phi_k', Phi_{k+1} = Phi_k^2, until max|Phi_k X Phi_k'| <= tol max(1, max|X|) and
+ * max|Phi_{k+1}| <= 1e-3; max_iter 0 -> 40, tol 0 -> 4 DBL_EPSILON.  A finish ORs the status words and writes
+ * residual[B] (optional): max(max|X_out - X*| / max(1, max|X*|), max|y_out - y*| / max(1, max|y*|)) for the adjoint that
+ * leaves the last segment of pass C, a self-check; iterations[B] (optional): the Smith steps.
+ * Stride-0 sums: a batch stride of 0 sums over the batch through per-instance records in the workspace and the
+ * fixed-order two-stage sum of tfmpc_tvlqr_backward_vjp_f64 (chunks of 64, then a tree; no atomics); a requested output
+ * with a time stride of 0 and N > 1 is summed in the sweep in time order, and the call then runs with ONE segment.
+ * Checks, before any launch: B < 0, n, m, N <= 0: TFMPC_ERR_ARG; n > 32 or m > 32: TFMPC_ERR_UNSUPPORTED; segments < 1,
+ * max_iter < 0, tol < 0 or NaN: TFMPC_ERR_ARG; B == 0 is a no-op; a NULL model operand, K, k, V, v, fwd_status or status,
+ * a negative stride: TFMPC_ERR_ARG; more than INT32_MAX waves: TFMPC_ERR_UNSUPPORTED; a workspace that is NULL or too
+ * small: TFMPC_ERR_WORKSPACE; not 8-byte aligned: TFMPC_ERR_ARG.  The workspace is always required.  In doubles, every
+ * array rounded up to 64, with w = B P:
+ *   3 up64(w n n) + 2 up64(w n) + up64(B n n)      Psi_s, W_s, X_s; s_s, y_s; Phi
+ *   + for B > 1, sum over dF, df, dC, dc of up64(B N size) + up64(ceil(B / 64) N (n + m)^2)     the batch sum's records and
+ *                                                     partial sums, size = n (n + m), n, (n + m)^2, n + m
+ *   + up64(ceil((3 w + 2 B) / 2))                   the status words
+ * times 8 bytes: what tfmpc_tvlqr_periodic_vjp_workspace_bytes_f64 returns, enough for any choice of outputs and strides
+ * (0 for an invalid or unsupported argument); a call needs only the records of the outputs it sums.
+ * status[b]: the forward's word where fwd_status[b] is set; TFMPC_ST_NOT_PD for a non-positive Q_uu pivot;
+ * TFMPC_ST_SINGULAR for a zero pivot in I - Phi; TFMPC_ST_NOT_STABILISING when the doubling meets a non-finite value or
+ * does not stop within max_iter steps (a caller's own K may not be stabilising); TFMPC_ST_NAN for a non-finite y or
+ * outgoing adjoint.  A phase does not run on an instance an earlier phase flagged.  A flagged instance has NaN in its own
+ * gradient rows, in its residual and in every batch sum that contains it; no other instance is affected.  No atomics, no
+ * allocation, no sync: an instance's bits depend on neither B nor its position, and repeated calls give identical bits.
+ * kernel_name: "tvp_vjp_f64_wave16" (n <= 16 and m <= 16; 38.875 KiB of LDS in pass A) or "tvp_vjp_f64_wave32" (149.75
+ * KiB, one wave per CU), "unsupported", "invalid".  TFMPC_TVLQR_TP_PHASES = 1 .. 5 stops the call after pass A / stitch A
+ * / pass B / stitch B / pass C (TFMPC_TVLQR_TP_STOPPED; timing only). */
+size_t tfmpc_tvlqr_periodic_vjp_workspace_bytes_f64(int B, int n, int m, int N, int segments);
+const char *tfmpc_tvlqr_periodic_vjp_kernel_name_f64(int n, int m, int N, int segments);
+int tfmpc_tvlqr_periodic_vjp_f64(int B, int n, int m, int N,
+                                 const double *F, long sF_b, long sF_t, const double *f, long sf_b, long sf_t,
+                                 const double *C, long sC_b, long sC_t, const double *c, long sc_b, long sc_t,
+                                 const double *K, const double *k, const double *V, const double *v, const int32_t *fwd_status,
+                                 const double *gK, const double *gk, const double *gV, const double *gv,
+                                 double *dF, long sdF_b, long sdF_t, double *df, long sdf_b, long sdf_t,
+                                 double *dC, long sdC_b, long sdC_t, double *dc, long sdc_b, long sdc_t,
+                                 double *residual, int32_t *iterations, int32_t *status, int segments, int max_iter, double tol,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------- control-limited TV-LQR gradients --------
  * tfmpc_tvlqr_vjp_f32 at the optimum of the CONTROL-LIMITED problem, low <= u_t <= high.  low, high:
  * [m] per (b, t) with a batch and a time stride in elements (0 = shared), +-inf allowed.  Control i of instance b is HELD

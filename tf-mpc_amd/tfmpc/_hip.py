@@ -67,6 +67,12 @@ _SIGNATURES.update({
     "tfmpc_tvlqr_periodic_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I, _I]),
     "tfmpc_tvlqr_periodic_steady_state_f64": (_I, [_I, _I, _I, _I] + [_P, _L, _L] * 4 + [_I, _I, ctypes.c_double] + [_P] * 7
                                               + [_P, _Z, _P]),
+    # its gradients: B n m N, F f C c (+ batch, time strides), K k V v fwd_status, gK gk gV gv, dF df dC dc
+    # (+ batch, time strides), residual iterations status, segments max_iter tol, workspace workspace_bytes stream
+    "tfmpc_tvlqr_periodic_vjp_workspace_bytes_f64": (_Z, [_I, _I, _I, _I, _I]),
+    "tfmpc_tvlqr_periodic_vjp_kernel_name_f64": (ctypes.c_char_p, [_I, _I, _I, _I]),
+    "tfmpc_tvlqr_periodic_vjp_f64": (_I, [_I, _I, _I, _I] + [_P, _L, _L] * 4 + [_P] * 5 + [_P] * 4 + [_P, _L, _L] * 4
+                                     + [_P, _P, _P, _I, _I, ctypes.c_double] + [_P, _Z, _P]),
     "tfmpc_tvlqr_vjp_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     # states actions, g_states g_actions g_costs, dF df dC dc (+ batch, time strides), dCfin dcfin dx0 (+ batch stride)
     "tfmpc_tvlqr_vjp_f32": (_I, _TV_MODEL + [_P, _P, _P, _P, _P] + [_P, _L, _L] * 4 + [_P, _L] * 3 + [_P, _P, _Z, _P]),

@@ -10,3 +10,4 @@ from tfmpc.solvers.steady_state_grad import lqr_steady_state, lqr_steady_state_v
 from tfmpc.solvers.box_lqr_grad import box_lqr_solve, tvlqr_box_vjp  # noqa: E402,F401  (differentiable control-limited LQR, tfmpc_tvlqr_box_vjp_f32)
 from tfmpc.solvers.tvlqr_box import tvlqr_box_solve  # noqa: E402,F401  (control-limited TV-LQR forward, tfmpc_tvlqr_box_solve_f32)
 from tfmpc.solvers.tvlqr_backward_grad import tvlqr_backward, tvlqr_backward_vjp  # noqa: E402,F401  (differentiable Riccati recursion, tfmpc_tvlqr_backward_vjp_f32 / _f64)
+from tfmpc.solvers.tvlqr_grad import tvlqr_periodic_vjp  # noqa: E402,F401  (gradients of the periodic steady state, tfmpc_tvlqr_periodic_vjp_f64)

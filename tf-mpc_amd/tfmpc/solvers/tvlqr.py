@@ -24,8 +24,9 @@ adjoint (``tfmpc_tvlqr_vjp_time_parallel_f64``), which repeats n
 
 A model that REPEATS with period N, over an infinite horizon: ``periodic_steady_state`` /
 :func:`tvlqr_periodic_steady_state` take the time axis as one period and return the stationary cycle of gains and value
-functions with a per-instance status (``tfmpc_tvlqr_periodic_steady_state_f64``; double only, no
-gradients yet).
+functions with a per-instance status (``tfmpc_tvlqr_periodic_steady_state_f64``; double only).  Their
+gradients are opt-in, as the others': ``differentiable=True`` differentiates through the wrap-around adjoint
+(``tfmpc_tvlqr_periodic_vjp_f64``); :func:`tfmpc.solvers.tvlqr_periodic_vjp` is that VJP alone.
 """
 
 import collections
@@ -519,7 +520,20 @@ class TimeVaryingLQR:
         return out
 
     # -- the model as one period of an infinite horizon (tfmpc_tvlqr_periodic_steady_state_f64) -----
-    def periodic_steady_state(self, segments=None, max_iter=0, tol=0.0):
+    def default_periodic_vjp_segments(self, batch_size=None):
+        """The ``segments`` of the periodic steady state's backward (``tfmpc_tvlqr_periodic_vjp_f64``) where
+        none were given, fitted to profiles/tvlqr_periodic_grad_rate.json as :meth:`default_vjp_segments` was (measured, not
+        inherited from it).  A step of a segment costs 67 us (its three sweeps), a segment 7.6 us (its products in the two
+        serial stitches) and the call about 50 us (its launches), so the time is ``67 ceil(N / P) + 7.6 P + 50`` us, least at
+        ``P = sqrt(8.8 N)`` (67 at N = 512, where 64 measured best; 190 at N = 4096, where 128 and 256 tie within 2 %).
+        ``P`` is capped by the sweep waves that the batch leaves each compute unit (four: 16 at B = 64 and one segment at
+        B = 4096 measured best), and by N."""
+        B = max(batch_size if batch_size is not None else (self.batch_size or 1), 1)
+        N = self.horizon
+        cus = torch.cuda.get_device_properties(self.device).multi_processor_count if self.device.type == "cuda" else 256
+        return max(min(int(round((8.8 * N) ** 0.5)), (4 * cus) // B, N), 1)
+
+    def periodic_steady_state(self, segments=None, max_iter=0, tol=0.0, differentiable=False):
         """The model's time axis taken as ONE PERIOD of an infinite-horizon problem whose model repeats: the stationary
         cycle of gains and value functions, a :class:`PeriodicSteadyState` of float64 device tensors ``K[(B,)N,m,n]``,
         ``k[(B,)N,m,1]``, ``V[(B,)N,n,n]``, ``v[(B,)N,n,1]`` (``V[t], v[t]`` AT step t: ``V[0]`` is the value function at
@@ -535,27 +549,52 @@ class TimeVaryingLQR:
         solve that ends at phase ``L`` of the cycle.
 
         Double precision only (``NotImplementedError`` for an fp32 problem: build it with ``dtype=torch.float64``); the
-        periodic problem has no final cost (``ValueError`` if the problem carries ``C_final`` / ``c_final``); gradients
-        of the periodic solution are not implemented yet (``NotImplementedError`` if an operand requires grad)."""
+        periodic problem has no final cost (``ValueError`` if the problem carries ``C_final`` / ``c_final``).
+
+        Gradients are opt-in: with ``differentiable=True``, autograd recording and a tensor operand requiring grad, ``K, k,
+        V, v`` are in the autograd graph of the caller's operands (taken to double inside the graph) and keep the bits of
+        the call without the flag -- the forward launch is unchanged, on the detached operands.  The backward is the
+        wrap-around adjoint (``tfmpc_tvlqr_periodic_vjp_f64``) with the forward's ``segments`` where they
+        were given, else :meth:`default_periodic_vjp_segments`, and this call's ``max_iter`` and ``tol`` for its Smith
+        doubling; an output the loss does not use is a NULL upstream pointer, every gradient is float64 in its operand's
+        shape (an operand without a batch axis: summed over the batch; a time axis of 1: summed over time), and
+        ``last_grad_status`` gets the backward's status.  Without the flag an operand that requires grad raises
+        ``NotImplementedError``."""
         if self.dtype != torch.float64:
             raise NotImplementedError("the periodic steady state is served in double only: build the problem with "
                                       "dtype=torch.float64")
         if self.C_final is not None:
             raise ValueError("the periodic infinite-horizon problem has no final cost: build the problem without "
                              "C_final / c_final")
-        if tvlqr_grad.wants_grad(*self._sources):
-            raise NotImplementedError("gradients of the periodic steady state are not implemented yet (a follow-up, "
-                                      "DESIGN.md 3.25): detach the operands")
+        wants = tvlqr_grad.wants_grad(*self._sources)
+        if wants and not differentiable:
+            raise NotImplementedError("gradients of the periodic steady state are opt-in: pass differentiable=True to "
+                                      "periodic_steady_state / tvlqr_periodic_steady_state for the wrap-around adjoint "
+                                      "(DESIGN.md 3.26), or detach the operands")
         if segments is not None and int(segments) < 1:
             raise ValueError(f"segments must be at least 1, got {segments}")
         max_iter, tol = int(max_iter), float(tol)
         if max_iter < 0 or not tol >= 0.0:
             raise ValueError(f"max_iter and tol must not be negative, got {max_iter}, {tol}")
-        lib = _hip.require_gpu()
-        n, m, N = self.state_size, self.action_size, self.horizon
         B = self.batch_size
         Bk = B if B is not None else 1
-        segments = self.default_segments(Bk) if segments is None else int(segments)
+        given = segments is not None
+        segments = int(segments) if given else self.default_segments(Bk)
+        if wants:
+            from tfmpc.solvers.tvlqr_backward_grad import tv_graph_operands
+            out = tvlqr_grad.PeriodicSteadyStateFunctionF64.apply(
+                self, lambda: self._periodic_launch(segments, max_iter, tol),
+                segments if given else self.default_periodic_vjp_segments(Bk), max_iter, tol, *tv_graph_operands(self)[:4])
+        else:
+            out = self._periodic_launch(segments, max_iter, tol)
+        return PeriodicSteadyState(*(out if B is not None else (t[0] for t in out)))
+
+    def _periodic_launch(self, segments, max_iter, tol):
+        """One tfmpc_tvlqr_periodic_steady_state_f64 call: batched ``K, k, V, v, residual, iterations, status``; sets
+        ``last_status``."""
+        lib = _hip.require_gpu()
+        n, m, N = self.state_size, self.action_size, self.horizon
+        Bk = self.batch_size if self.batch_size is not None else 1
         dev, dt = self.device, self.dtype
         K = torch.empty((Bk, N, m, n), device=dev, dtype=dt)
         k = torch.empty((Bk, N, m, 1), device=dev, dtype=dt)
@@ -572,8 +611,7 @@ class TimeVaryingLQR:
             workspace.numel() * 8, _hip.stream())
         _hip.check(rc, "tfmpc_tvlqr_periodic_steady_state_f64")
         self.last_status = status
-        out = (K, k, V, v, residual, iterations, status)
-        return PeriodicSteadyState(*(out if B is not None else (t[0] for t in out)))
+        return K, k, V, v, residual, iterations, status
 
     def solve(self, x0, differentiable=False):
         """A :class:`Trajectory`; with autograd recording and an operand or ``x0`` requiring grad, a
@@ -650,16 +688,18 @@ def tvlqr_solve_time_parallel(F, f, C, c, x0, segments=None, C_final=None, c_fin
     return (states, actions, costs) if out["batched"] else (states[0], actions[0], costs[0])
 
 
-def tvlqr_periodic_steady_state(F, f, C, c, segments=None, max_iter=0, tol=0.0):
+def tvlqr_periodic_steady_state(F, f, C, c, segments=None, max_iter=0, tol=0.0, differentiable=False):
     """:meth:`TimeVaryingLQR.periodic_steady_state` on operands in :class:`TimeVaryingLQR`'s shapes, their time axis one
     period: a :class:`PeriodicSteadyState`.  ``F`` must be float64 (tensor or numpy): an fp32 problem raises
-    ``NotImplementedError``, as does an operand that requires grad (gradients of the periodic solution are a follow-up)."""
+    ``NotImplementedError``, as does an operand that requires grad -- unless ``differentiable=True``: ``K, k, V, v`` are
+    then in the autograd graph of every tensor operand that requires grad, with fp64 gradients from the wrap-around
+    adjoint (``tfmpc_tvlqr_periodic_vjp_f64``)."""
     kind = F.dtype if isinstance(F, torch.Tensor) else np.asarray(F).dtype
     if kind not in (torch.float64, np.float64):
         raise NotImplementedError(f"the periodic steady state is served in double only (dtype=torch.float64), F is {kind}")
     device = next((t.device for t in (F, f, C, c) if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
     tv = TimeVaryingLQR(F, f, C, c, device=device, dtype=torch.float64)
-    return tv.periodic_steady_state(segments, max_iter, tol)
+    return tv.periodic_steady_state(segments, max_iter, tol, differentiable)
 
 
 __all__ = ["TimeVaryingLQR", "PeriodicSteadyState", "tvlqr_solve_time_parallel", "tvlqr_periodic_steady_state"]

@@ -299,5 +299,98 @@ def tvlqr_vjp_time_parallel(F, f, C, c, states, actions, K, V, v, g_states=None,
     return (*grads, status)
 
 
-__all__ = ["SolveFunction", "SolveFunctionF64", "SolveTimeParallelFunctionF64", "TensorTrajectory", "tvlqr_solve",
-           "tvlqr_vjp_time_parallel"]
+def periodic_vjp_f64(tv, K, k, V, v, fwd_status, ups, shapes, needed, segments, max_iter=0, tol=0.0):
+    """One tfmpc_tvlqr_periodic_vjp_f64 call on the double problem ``tv``, whose time axis is one period.
+    ``K, k, V, v, fwd_status``: the periodic forward's batched outputs; ``ups``: ``gK, gk, gV, gv`` (``None`` = zero, a NULL
+    pointer).  One double gradient per entry of ``shapes`` (``F, f, C, c`` as the solver shapes them) that ``needed`` asks
+    for -- summed over the batch where the shape has no batch axis, over time where its time axis is 1 -- then
+    ``residual[B]``, ``iterations[B]`` (the Smith steps) and the backward's ``status[B]``."""
+    lib = _hip.require_gpu()
+    Bk, N, m, n = K.shape
+    dev, f64 = K.device, torch.float64
+    grads = alloc_grads(shapes, needed, Bk, dev, f64)
+    args = []
+    for g in grads:
+        args += [_hip.ptr(g), *grad_strides(g, 4, True)]
+    ups = [None if g is None else g.to(device=dev, dtype=f64).contiguous() for g in ups]
+    alloc = torch.zeros if Bk == 0 else torch.empty
+    residual = alloc((Bk,), dtype=f64, device=dev)
+    iterations = alloc((Bk,), dtype=torch.int32, device=dev)
+    status = alloc((Bk,), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.tfmpc_tvlqr_periodic_vjp_workspace_bytes_f64(Bk, n, m, N, segments))
+    ws = torch.empty((max(ws_bytes // 8, 1),), dtype=f64, device=dev)
+    rc = lib.tfmpc_tvlqr_periodic_vjp_f64(Bk, n, m, N, *tv._model_args()[:12], _hip.ptr(K), _hip.ptr(k), _hip.ptr(V), _hip.ptr(v),
+                                          _hip.ptr(fwd_status), *(_hip.ptr(u) for u in ups), *args, _hip.ptr(residual),
+                                          _hip.ptr(iterations), _hip.ptr(status), segments, max_iter, tol, _hip.ptr(ws),
+                                          ws.numel() * 8, _hip.stream())
+    _hip.check(rc, "tfmpc_tvlqr_periodic_vjp_f64")
+    return grads, residual, iterations, status
+
+
+class PeriodicSteadyStateFunctionF64(torch.autograd.Function):
+    """The periodic steady state in the autograd graph: the forward is the unchanged
+    ``tfmpc_tvlqr_periodic_steady_state_f64`` launch of ``tv`` (which holds the detached operands), so every output keeps
+    its bits; the backward is ``tfmpc_tvlqr_periodic_vjp_f64`` with ``vjp_segments``.  ``residual``, ``iterations`` and
+    ``status`` are not differentiable.  ``tv.last_grad_status`` gets the backward's status."""
+
+    @staticmethod
+    def forward(ctx, tv, launch, vjp_segments, max_iter, tol, F, f, C, c):
+        K, k, V, v, residual, iterations, status = launch()
+        ctx.tv, ctx.call = tv, (vjp_segments, max_iter, tol)
+        ctx.shapes = [t.shape for t in (F, f, C, c)]
+        ctx.save_for_backward(K, k, V, v, status)
+        ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None: a NULL upstream pointer
+        ctx.mark_non_differentiable(residual, iterations, status)
+        return K, k, V, v, residual, iterations, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gK, gk, gV, gv, *_):
+        K, k, V, v, fwd_status = ctx.saved_tensors
+        grads, _, _, status = periodic_vjp_f64(ctx.tv, K, k, V, v, fwd_status, (gK, gk, gV, gv), ctx.shapes,
+                                               ctx.needs_input_grad[5:], *ctx.call)
+        ctx.tv.last_grad_status = status
+        return (None,) * 5 + tuple(grads)
+
+
+def tvlqr_periodic_vjp(F, f, C, c, K, k, V, v, fwd_status, gK=None, gk=None, gV=None, gv=None, segments=None, max_iter=0,
+                       tol=0.0):
+    """The vector-Jacobian product of the periodic steady state alone, in double (``tfmpc_tvlqr_periodic_vjp_f64``,
+    DESIGN.md 3.26), for any forward: ``K, k, V, v, fwd_status`` as :func:`tvlqr_periodic_steady_state` of ``(F, f, C, c)``
+    gave them (batched, or without a batch axis when no operand has one), ``gK, gk, gV, gv`` the upstream gradients
+    (``None`` = zero).  ``segments=None`` picks :meth:`TimeVaryingLQR.default_periodic_vjp_segments`; ``max_iter=0`` is 40
+    Smith steps, ``tol=0`` is 4 ``DBL_EPSILON``.  Returns ``(dF, df, dC, dc, residual, iterations, status)``: each gradient
+    float64 in its operand's shape as :class:`TimeVaryingLQR` holds it (vectors as columns; an operand without a batch axis
+    gets the sum over the batch, a time axis of 1 the sum over time -- the call then sweeps the period as one segment),
+    ``residual[(B)]`` the fixed point's self-check, ``iterations[(B)]`` the Smith steps and the per-instance status -- the
+    forward's where that was flagged; a flagged instance has NaN in its own gradient rows and in every sum that contains
+    it.  A ``K`` of the caller's own that is not stabilising is ``TFMPC_ST_NOT_STABILISING``."""
+    from tfmpc.solvers.tvlqr import TimeVaryingLQR, _as_dtype
+    f64 = torch.float64
+    device = next((t.device for t in (F, f, C, c, K) if isinstance(t, torch.Tensor) and t.device.type != "cpu"), None)
+    tv = TimeVaryingLQR(F, f, C, c, device=device, dtype=f64)
+    dev = tv.device
+    n, m, N = tv.state_size, tv.action_size, tv.horizon
+    batched = tv.batch_size is not None
+    Bk = tv.batch_size if batched else 1
+    K, k, V, v = (_as_dtype(t, dev, f64).reshape(-1, N, *inner).contiguous()
+                  for t, inner in ((K, (m, n)), (k, (m, 1)), (V, (n, n)), (v, (n, 1))))
+    fwd_status = torch.as_tensor(fwd_status).detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if any(t.shape[0] != Bk for t in (K, k, V, v, fwd_status)):
+        raise ValueError("K, k, V, v and fwd_status must share the operands' batch size")
+    ups = [None if g is None else _as_dtype(g, dev, f64).reshape(Bk, N, *inner)
+           for g, inner in ((gK, (m, n)), (gk, (m, 1)), (gV, (n, n)), (gv, (n, 1)))]
+    segments = tv.default_periodic_vjp_segments(Bk) if segments is None else int(segments)
+    max_iter, tol = int(max_iter), float(tol)
+    if segments < 1 or max_iter < 0 or not tol >= 0.0:
+        raise ValueError(f"segments must be at least 1 and max_iter, tol not negative, got {segments}, {max_iter}, {tol}")
+    shapes = [t.shape for t in (tv.F, tv.f, tv.C, tv.c)]
+    grads, residual, iterations, status = periodic_vjp_f64(tv, K, k, V, v, fwd_status, ups, shapes, (True,) * 4, segments,
+                                                           max_iter, tol)
+    tv.last_grad_status = status
+    tail = (residual, iterations, status) if batched else (residual[0], iterations[0], status[0])
+    return (*grads, *tail)
+
+
+__all__ = ["SolveFunction", "SolveFunctionF64", "SolveTimeParallelFunctionF64", "PeriodicSteadyStateFunctionF64",
+           "TensorTrajectory", "tvlqr_solve", "tvlqr_vjp_time_parallel", "tvlqr_periodic_vjp"]
