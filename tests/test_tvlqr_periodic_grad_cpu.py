@@ -2,7 +2,7 @@
 the numpy restatement of tests/tvlqr_periodic_grad_ref.py against the brute-force tiled recursion and against central
 differences of the periodic solve, across segment counts, against the stationary gradients at N = 1, and the
 attainability of the budget rule on every input of the GPU accuracy test; then the C ABI's workspace formula, kernel
-names and argument checks, none of which launches anything.
+names and argument checks, none of which launches anything, and the kernels' resources from their device assembly.
 
 The budget rule is DESIGN.md 3.14 / 3.23's: per gradient and instance, error against the longdouble restatement over
 max(budget, 2^-48 max(1, |ref|)); median over instances <= 2.5 and every instance <= 10."""
@@ -10,6 +10,9 @@ import ctypes
 import functools
 import os
 import re
+import subprocess
+import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -24,6 +27,8 @@ import tvlqr_time_parallel_ref as tp
 from tfmpc import _hip, solvers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import check_ring_waits  # noqa: E402
 LD = np.longdouble
 B = 3
 GRADS = pg.GRADS
@@ -217,3 +222,43 @@ def test_the_refusal_names_the_flag():
     with pytest.raises(NotImplementedError, match="gradients") as err:
         solvers.tvlqr_periodic_steady_state(*leaves)
     assert "differentiable=True" in str(err.value)
+
+
+@pytest.mark.skipif(check_ring_waits.hipcc_path() is None, reason="needs the device compiler (hipcc) to produce the assembly")
+def test_the_f64_kernels_use_no_scratch_no_static_lds_and_the_f64_matrix_cores():
+    """The periodic file's counterpart of tests/test_tvlqr_backward_grad_f64_cpu.py's resource test: the exact set of 13
+    kernels -- the shared sweep tvb_vjp_f64_kernel (tvlqr_backward_vjp_body.h) at both widths in its three passes, the four
+    stitches, the finish, the two double batch-sum stages."""
+    path = os.path.join(ROOT, "tf-mpc_amd", "csrc", "tvlqr_periodic_vjp_f64.hip")
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "k.s")
+        subprocess.run([check_ring_waits.hipcc_path(), *check_ring_waits.FLAGS, "--cuda-device-only", "-S", path, "-o", out], check=True,
+                       capture_output=True)
+        text = open(out).read()
+    found = re.findall(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
+                       r"\s+\.vgpr_spill_count:\s+(\d+)", text)
+    assert len(found) == 13 == len(re.findall(r"^\s*\.amdhsa_kernel\s", text, flags=re.M)), found
+    names = [f[0] for f in found]
+    sweeps = sorted(name for name in names if "tvb_vjp_f64_kernel" in name)
+    assert len(set(sweeps)) == 6, found
+    assert all(sum(f"ILi{np_}ENS0_8PeriodicILi{p}EEE" in name for name in sweeps) == 1 for np_ in (16, 32) for p in (0, 1, 2)), sweeps
+    stitches = sorted(name for name in names if "tvp_vjp_f64_stitch_kernel" in name)
+    assert len(set(stitches)) == 4, found
+    assert all(sum(f"ILi{np_}ELi{mode}EEE" in name for name in stitches) == 1 for np_ in (16, 32) for mode in (0, 1)), stitches
+    assert sum("tvp_vjp_f64_finish_kernel" in name for name in names) == 1, found
+    sums = sorted(name for name in names if "batch_sum_" in name)
+    assert len(sums) == 2 and "batch_sum_stage1" in sums[0] and "batch_sum_stage2_tree" in sums[1], found
+    assert all(name.endswith("PKdimPd") for name in sums), sums            # the double overloads
+    for name, private, vgprs, spills in found:
+        assert int(private) == 0 and int(spills) == 0 and int(vgprs) <= 256, (name, private, vgprs, spills)
+    # the sweeps take all their LDS at launch (none static); the launch sizes are the layout's
+    static = {name: int(size) for size, name in
+              re.findall(r"\.group_segment_fixed_size:\s+(\d+)\n(?:(?!\s+\.group_segment_fixed_size).*\n)*?\s+\.name:\s+(\S+)\n", text)}
+    assert all(static[name] == 0 for name in sweeps), static
+    assert "BvLayout<16>::total(kPassA) == 4976 && BvLayout<32>::total(kPassA) == 19168" in open(path).read()
+    assert 19168 * 8 <= 160 * 1024
+    # the f64 matrix-core instruction is in every sweep and stitch body
+    for name in sweeps + stitches:
+        body = text[text.index(name + ":"):]
+        body = body[:body.index(".Lfunc_end")]
+        assert "v_mfma_f64_16x16x4" in body, name

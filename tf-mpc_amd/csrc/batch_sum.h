@@ -68,6 +68,32 @@ inline BatchSumPlan batch_sum_plan(int B, int chunk, int count, const int *size,
     return p;
 }
 
+// Which outputs are summed, for batch_sum_plan: bit q is set where outs[q] has batch stride sb[q] == 0 (over a batch of
+// one the sum is the instance's own gradient, written in place).  With time strides st, slots[q] = steps for an output
+// that has a time axis (st[q] != 0), else 1; a family without a time axis passes st = slots = nullptr.
+template <class T>
+inline unsigned batch_sum_select(int B, int count, T *const *outs, const long *sb, const long *st, int steps, int *slots)
+{
+    unsigned summed = 0;
+    for (int q = 0; q < count; ++q) {
+        if (slots) slots[q] = st[q] ? steps : 1;
+        if (outs[q] && sb[q] == 0 && B > 1) summed |= 1u << q;
+    }
+    return summed;
+}
+
+// Where the instance kernel writes output q: set(q, pointer, batch stride, time stride) gets the caller's buffer and
+// strides, or for a summed output its records in the workspace w, [B][slots][size] (st = nullptr: no time strides, 0).
+template <class T, class Set>
+inline void batch_sum_route(const BatchSumPlan &p, T *w, T *const *outs, const long *sb, const long *st, Set set)
+{
+    for (int q = 0; q < p.count; ++q) {
+        const long size = p.size[q], t = st ? st[q] : 0;
+        if (p.summed >> q & 1u) set(q, w + p.rec_off[q], (long)p.slots[q] * size, t ? size : 0);
+        else set(q, outs[q], sb[q], t);
+    }
+}
+
 // Enqueues stage 1 and stage 2 of every summed output: outs[q] with time stride st[q] (in-order stage 2; the tree writes
 // one slot).  CHUNK is the chunk the plan was made with.  The caller returns on !p.fits before it launches anything.
 template <int CHUNK, BatchSumOrder ORDER, class T = float>

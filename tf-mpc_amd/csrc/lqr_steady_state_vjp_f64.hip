@@ -343,10 +343,8 @@ int tfmpc_lqr_steady_state_vjp_f64(int B, int n, int m,
         if (s < 0) return TFMPC_ERR_ARG;
     double *outs[kOuts] = {dF, df, dC, dc};
     const long strides[kOuts] = {sdF_b, sdf_b, sdC_b, sdc_b};
-    // a stride of 0 sums over the batch; over a batch of one the sum is the instance's own gradient, written in place
-    unsigned summed = 0;
-    for (int q = 0; q < kOuts; ++q)
-        if (outs[q] && strides[q] == 0 && B > 1) summed |= 1u << q;
+    // a stride of 0 sums over the batch (no time axis here)
+    const unsigned summed = batch_sum_select(B, kOuts, outs, strides, nullptr, 1, nullptr);
     const BatchSumPlan plan = sum_plan(B, n, m, summed);
     if (!plan.fits) return TFMPC_ERR_UNSUPPORTED;
     if (plan.floats && (!workspace || workspace_bytes < plan.floats * sizeof(double))) return TFMPC_ERR_WORKSPACE;
@@ -360,10 +358,7 @@ int tfmpc_lqr_steady_state_vjp_f64(int B, int n, int m,
     a.sF = sF_b; a.sf = sf_b; a.sC = sC_b; a.sc = sc_b;
     a.K = K; a.k = k; a.P = P; a.p = p; a.fwd_status = fwd_status;
     a.gK = gK; a.gk = gk; a.gP = gP; a.gp = gp;
-    for (int q = 0; q < kOuts; ++q) {
-        if (summed >> q & 1u) a.o[q] = {w + plan.rec_off[q], (long)plan.size[q]};
-        else a.o[q] = {outs[q], strides[q]};
-    }
+    batch_sum_route(plan, w, outs, strides, nullptr, [&](int q, double *p, long b, long) { a.o[q] = {p, b}; });
     a.status = status;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int rc = wave16(n, m) ? launch_for<16>(a, s) : launch_for<32>(a, s);

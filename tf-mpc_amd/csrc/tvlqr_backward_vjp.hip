@@ -13,6 +13,8 @@
 //   Vbar <- sym(F_t Qbar F_t' + rbar f_t' + abar f_t f_t' / 2),  vbar <- rbar + abar f_t
 // and after the last step Vbar, vbar are the final cost's gradient (added into dC_{T-1}[:n,:n], dc_{T-1}[:n] for the default
 // final cost).  The Riccati recursion is not recomputed: the sweep reads the model and the forward's outputs only.
+// tvlqr_backward_vjp_body.h is this sequence, statement for statement, in double (the finite and the periodic VJP): a change
+// to the step belongs in this file and in that header (one precision-generic body changes every kernel's text: DESIGN.md 3.26).
 //
 // Layout as lqr_steady_state_vjp.hip: every matrix of the step in the wave's LDS slice, every product on
 // v_mfma_f32_16x16x4_f32 (wave_ops.h mfma_matmul, strict fp32).  NP = 16 serves n <= 16, NP = 32 serves n <= 32, both with
@@ -263,13 +265,9 @@ int tfmpc_tvlqr_backward_vjp_f32(int B, int n, int m, int T,
     float *outs[kOuts] = {dF, df, dC, dc, dCfin, dcfin};
     const long sb[kOuts] = {sdF_b, sdf_b, sdC_b, sdc_b, sdCfin_b, sdcfin_b};
     const long st[kOuts] = {sdF_t, sdf_t, sdC_t, sdc_t, 0, 0};
-    // a batch stride of 0 sums over the batch; over a batch of one the sum is the instance's own gradient, written in place
-    unsigned summed = 0;
+    // a batch stride of 0 sums over the batch
     int slots[kOuts];
-    for (int q = 0; q < kOuts; ++q) {
-        slots[q] = st[q] ? T : 1;
-        if (outs[q] && sb[q] == 0 && B > 1) summed |= 1u << q;
-    }
+    const unsigned summed = batch_sum_select(B, kOuts, outs, sb, st, T, slots);
     const BatchSumPlan plan = sum_plan(B, n, m, slots, summed);
     if (!plan.fits) return TFMPC_ERR_UNSUPPORTED;                  // the batch sum's blocks are one grid axis
     if (plan.floats && (!workspace || workspace_bytes < plan.floats * sizeof(float))) return TFMPC_ERR_WORKSPACE;
@@ -282,11 +280,7 @@ int tfmpc_tvlqr_backward_vjp_f32(int B, int n, int m, int T,
     a.Cfin = Cfin; a.cfin = cfin; a.sCfin_b = sCfin_b; a.scfin_b = scfin_b;
     a.K = K; a.k = k; a.V = V; a.v = v; a.fwd_status = fwd_status;
     a.gK = gK; a.gk = gk; a.gV = gV; a.gv = gv; a.gconst = gconst;
-    for (int q = 0; q < kOuts; ++q) {
-        const long size = plan.size[q];
-        if (summed >> q & 1u) a.o[q] = {w + plan.rec_off[q], (long)slots[q] * size, st[q] ? size : 0};
-        else a.o[q] = {outs[q], sb[q], st[q]};
-    }
+    batch_sum_route(plan, w, outs, sb, st, [&](int q, float *p, long b, long t) { a.o[q] = {p, b, t}; });
     a.status = status;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n <= 16) hipLaunchKernelGGL(tvb_vjp_kernel<16>, dim3(B), dim3(kWave), 0, s, a);

@@ -3,16 +3,10 @@
 //
 // Given the stationary cycle K_t, k_t, V_t, v_t of one period of N steps (tfmpc_tvlqr_periodic_steady_state_f64) and
 // upstream gradients gK, gk, gV, gv, the adjoint of the Riccati recursion is swept FORWARD in time carrying Vbar (n x n,
-// symmetric) and vbar (n), the adjoints of V_t and v_t.  Step t is tvlqr_backward_vjp_f64.hip's with abar = 0 (the
-// infinite horizon has no const output) and P = V_{(t+1) % N}, s = v_{(t+1) % N}; it is RESTATED here, statement for
-// statement, because sharing a device function with tvb_vjp_f64_kernel changed that kernel's instruction text -- a
-// change to the step belongs in both files:
-//   Vbar += sym(gV_t), vbar += gv_t
-//   Quu = C_t,uu + F_t,u' P F_t,u;  [Kt | kt] = -Quu^-1 [gK_t | gk_t]   (elimination without pivoting: NOT_PD on a pivot <= 0)
-//   qbar = [vbar; kt + K vbar]
-//   Qbar_xx = Vbar,  Qbar_ux = (KV + G + k vbar') / 2,  Qbar_uu = sym(G K' + qbar_u k'),  KV = K Vbar, G = KV + Kt
-//   dC_t = Qbar, dc_t = qbar;  r = P f_t + s, rbar = F_t qbar;  dF_t = 2 (P F_t) Qbar + r qbar',  df_t = P rbar
-//   Vbar <- sym(F_t Qbar F_t' + rbar f_t'),  vbar <- rbar
+// symmetric) and vbar (n), the adjoints of V_t and v_t.  The step and its kernel template are
+// tvlqr_backward_vjp_body.h's (shared with the finite horizon, tvlqr_backward_vjp_f64.hip).  This file is the PERIODIC
+// mode -- abar = 0 (the infinite horizon has no const output), P = V_{(t+1) % N}, s = v_{(t+1) % N}, one wave per
+// (instance, segment), three passes that differ in the incoming adjoint and in what they keep -- and what closes the lap.
 // The period has no final cost: the adjoint that leaves step N - 1 is the adjoint of V_N = V_0 and re-enters step 0.  One
 // lap maps the adjoint (X, y) that enters phase 0 from the wrap to
 //   y_out = Phi y + s_y,  X_out = Phi X Phi' + L(y) + S_X,   Phi = A_cl,N-1 ... A_cl,0,  A_cl,t = F_t,x + F_t,u K_t,
@@ -45,26 +39,17 @@
 #include "batch_sum.h"
 #include "launch.h"
 #include "options.h"
-#include "tvlqr_kernels.h"
-#include "wave_ops_f64.h"
+#include "tvlqr_backward_vjp_body.h"
 
 namespace tfmpc {
 
 namespace {
 
-using T = double;
-
 constexpr int kRedChunk = 64;          // instances per stage-1 block of the batch sum
 constexpr double kSmithPhiZero = 1e-3;
 constexpr int kSmithMaxIter = 40;      // DESIGN.md 3.25's defaults
 constexpr double kSmithTol = 4.0 * DBL_EPSILON;
-enum { kOutF, kOutf, kOutC, kOutc, kOuts };
-enum { kPassA, kPassB, kPassC };
-
-struct PvOut {
-    double *p;
-    long sb, st;      // batch / time stride in elements (a workspace record when the caller's batch stride is 0)
-};
+constexpr int kOuts = kOutc + 1;       // dF, df, dC, dc
 
 struct PvArgs {
     int B, n, m, N, segments, len;
@@ -73,7 +58,7 @@ struct PvArgs {
     const double *K, *k, *V, *v;
     const int32_t *fwd_status;
     const double *gK, *gk, *gV, *gv;
-    PvOut o[kOuts];
+    BvOut o[kOuts];
     double *Psi, *Ws, *Xs;             // per (b, segment) [n][n]: prod A_cl; outgoing Vbar of pass B, then C; incoming X
     double *sv, *ys;                   // per (b, segment) [n]: outgoing vbar of pass A, then C; incoming y
     double *Phi;                       // per instance [n][n]: the closed-loop monodromy
@@ -86,167 +71,17 @@ struct PvArgs {
     int32_t *status;
 };
 
-__device__ __forceinline__ void emit(const PvOut &o, int b, int t, int e, double x)
-{
-    double *p = o.p + (size_t)b * o.sb + (size_t)t * o.st + e;
-    if (o.st == 0 && t > 0) x += *p;   // time-shared: accumulate in time order (one segment; this lane owns element e)
-    *p = x;
-}
-
-// tvlqr_backward_vjp_f64.hip's NP-wide LDS layout; pass A adds the running product Psi [NP][NP + 1]
-template <int NP>
-struct PvLayout {
-    static constexpr int DP = 2 * NP, LDN = NP + 1, LDD = DP + 1, LDA = 2 * NP + 3;
-    static constexpr int kWide = NP * LDD, kSq = NP * LDN, kAug = NP * LDA;
-    static constexpr int kBody = 5 * kWide + 5 * kSq + kAug + 9 * NP;
-    static constexpr int total(int pass) { return kBody + (pass == kPassA ? kSq : 0); }
+// the mode of tvb_vjp_f64_kernel (tvlqr_backward_vjp_body.h): which of the three sweeps
+template <int PASS>
+struct Periodic {
+    using Args = PvArgs;
+    static constexpr bool kPeriodic = true;
+    static constexpr int kPass = PASS;
+    static __device__ int steps(const PvArgs &a) { return a.N; }
 };
-static_assert(PvLayout<16>::total(kPassA) == 4976 && PvLayout<32>::total(kPassA) == 19168,
+
+static_assert(BvLayout<16>::total(kPassA) == 4976 && BvLayout<32>::total(kPassA) == 19168,
               "DESIGN.md 3.26: 38.875 KiB and 149.75 KiB in pass A, 36.75 KiB and 141.5 KiB in passes B and C");
-
-// NP: the compile-time bound on n and m (16 or 32).  PASS: which of the three sweeps.
-template <int NP, int PASS>
-__global__ __launch_bounds__(kWave) void tvp_vjp_f64_sweep_kernel(PvArgs a)
-{
-    using Lay = PvLayout<NP>;
-    constexpr int LDN = Lay::LDN, LDD = Lay::LDD, LDA = Lay::LDA, WD = Lay::kWide, SQ = Lay::kSq;
-    extern __shared__ double tvp_vjp_smem_f64[];
-    T *const sF = tvp_vjp_smem_f64, *const sPF = sF + WD, *const sT = sPF + WD, *const sQb = sT + WD;
-    T *const sP = sQb + 2 * WD, *const sVb = sP + SQ, *const sK = sVb + SQ, *const sKV = sK + SQ, *const sG = sKV + SQ;
-    T *const aug = sG + SQ;
-    T *const vf = aug + Lay::kAug, *const vs = vf + NP, *const vk = vs + NP, *const vvb = vk + NP, *const vr = vvb + NP;
-    T *const vrb = vr + NP, *const vq = vrb + NP, *const fac = vq + 2 * NP;
-    T *const sPsi = fac + NP;          // pass A only
-
-    const int P = a.segments;
-    const size_t w = blockIdx.x;
-    const int b = (int)(blockIdx.x / (unsigned)P), seg = (int)blockIdx.x - b * P;
-    const int lane = lane_id();
-    const int n = a.n, m = a.m, N = a.N, d = n + m;
-    const int t0 = seg * a.len, t1 = N - t0 < a.len ? N : t0 + a.len;
-    int32_t *const word = (PASS == kPassA ? a.st_a : PASS == kPassB ? a.st_b : a.st_c) + w;
-    // an instance that an earlier phase flagged is not swept
-    if (PASS == kPassA ? a.fwd_status[b] : PASS == kPassB ? a.st_sa[b] : a.st_sb[b]) {
-        if (lane == 0) *word = 0;
-        return;
-    }
-    int status = 0;
-    auto zero = [](int, int) { return T(0); };
-    const PvOut &oF = a.o[kOutF], &of = a.o[kOutf], &oC = a.o[kOutC], &oc = a.o[kOutc];
-
-    // the incoming adjoint: (0, 0), (0, y_s) or (X_s, y_s)
-    wave_for_2d(n, n, [&](int i, int j, int idx) {
-        sVb[i * LDN + j] = PASS == kPassC ? a.Xs[w * n * n + idx] : T(0);
-        if (PASS == kPassA) sPsi[i * LDN + j] = i == j ? T(1) : T(0);
-    });
-    for (int i = lane; i < n; i += kWave) vvb[i] = PASS == kPassA ? T(0) : a.ys[w * n + i];
-
-    for (int t = t0; t < t1; ++t) {
-        const size_t bt = (size_t)b * N + t;
-        const size_t bn = (size_t)b * N + (t + 1 == N ? 0 : t + 1);       // the period wraps: V_N = V_0
-        const T *Ft = tv_at(a.F, a.sF_b, a.sF_t, b, t), *ft = tv_at(a.f, a.sf_b, a.sf_t, b, t);
-        const T *Cg = tv_at(a.C, a.sC_b, a.sC_t, b, t);
-        const T *Pg = a.V + bn * n * n, *sg = a.v + bn * n;
-        load_matrix(sF, LDD, Ft, n, d);
-        load_matrix(sK, LDN, a.K + bt * m * n, m, n);
-        wave_for_2d(n, n, [&](int i, int j, int idx) {
-            sP[i * LDN + j] = Pg[idx];
-            if (a.gV) sVb[i * LDN + j] += T(0.5) * (a.gV[bt * n * n + idx] + a.gV[bt * n * n + j * n + i]);
-        });
-        for (int i = lane; i < n; i += kWave) {
-            vf[i] = ft[i];
-            vs[i] = sg[i];
-            if (a.gv) vvb[i] += a.gv[bt * n + i];
-        }
-        for (int r = lane; r < m; r += kWave) vk[r] = a.k[bt * m + r];
-        // aug = [Quu | gK_t | gk_t]  (m rows)
-        wave_for_2d(m, n + 1, [&](int r, int j, int) {
-            aug[r * LDA + m + j] = j < n ? (a.gK ? a.gK[bt * m * n + r * n + j] : T(0)) : (a.gk ? a.gk[bt * m + r] : T(0));
-        });
-        wsync();
-
-        // PF = P F [n][d], KV = K Vbar [m][n], r = P f + s
-        wave_matmul_f64<NP>(n, d, n, [&](int i, int kk) { return sP[i * LDN + kk]; }, [&](int kk, int j) { return sF[kk * LDD + j]; },
-                            zero, [&](int i, int j, T x) { sPF[i * LDD + j] = x; });
-        wave_matmul_f64<NP>(m, n, n, [&](int i, int kk) { return sK[i * LDN + kk]; }, [&](int kk, int j) { return sVb[kk * LDN + j]; },
-                            zero, [&](int i, int j, T x) { sKV[i * LDN + j] = x; });
-        wave_matvec<T>(n, n, [&](int i, int j) { return sP[i * LDN + j]; }, [&](int j) { return vf[j]; },
-                       [&](int i, T s) { vr[i] = s + vs[i]; });
-        lds_sync();
-        // Quu = C_uu + F_u' (P F)_u, symmetrised as in the forward
-        wave_matmul_f64<NP>(m, m, n, [&](int i, int kk) { return sF[kk * LDD + n + i]; }, [&](int kk, int j) { return sPF[kk * LDD + n + j]; },
-                            [&](int i, int j) { return Cg[(n + i) * d + n + j]; }, [&](int i, int j, T x) { aug[i * LDA + j] = x; });
-        wsync();
-        symmetrise(aug, LDA, m);
-        wsync();
-        if (wave_gauss_jordan<false, T>(aug, LDA, m, m + n + 1, fac, fac)) {
-            status |= TFMPC_ST_NOT_PD;
-            break;
-        }
-        // G = KV + Kt [m][n];  qbar = [vbar; kt + K vbar]
-        wave_for_2d(m, n, [&](int r, int j, int) { sG[r * LDN + j] = sKV[r * LDN + j] - aug[r * LDA + m + j]; });
-        for (int i = lane; i < n; i += kWave) vq[i] = vvb[i];
-        wave_matvec<T>(m, n, [&](int r, int j) { return sK[r * LDN + j]; }, [&](int j) { return vvb[j]; },
-                       [&](int r, T s) { vq[n + r] = s - aug[r * LDA + m + n]; });
-        lds_sync();
-        // Qbar: the uu block (symmetrised below), xx = Vbar, ux / xu;  rbar = F qbar
-        wave_matmul_f64<NP>(m, m, n, [&](int i, int kk) { return sG[i * LDN + kk]; }, [&](int kk, int j) { return sK[j * LDN + kk]; },
-                            [&](int i, int j) { return vq[n + i] * vk[j]; },
-                            [&](int i, int j, T x) { sQb[(n + i) * LDD + n + j] = x; });
-        wave_for_2d(n, n, [&](int i, int j, int) { sQb[i * LDD + j] = sVb[i * LDN + j]; });
-        wave_for_2d(m, n, [&](int r, int i, int) {
-            const T x = T(0.5) * (sKV[r * LDN + i] + sG[r * LDN + i] + vk[r] * vvb[i]);
-            sQb[(n + r) * LDD + i] = x;
-            sQb[i * LDD + n + r] = x;
-        });
-        wave_matvec<T>(n, d, [&](int i, int j) { return sF[i * LDD + j]; }, [&](int j) { return vq[j]; }, [&](int i, T s) { vrb[i] = s; });
-        lds_sync();
-        symmetrise(sQb + n * LDD + n, LDD, m);
-        lds_sync();
-        // dF = 2 (PF) Qbar + r qbar';  T = F Qbar [n][d];  df = P rbar
-        if (PASS == kPassC && oF.p)
-            wave_matmul_f64<2 * NP>(n, d, d, [&](int i, int kk) { return sPF[i * LDD + kk]; },
-                                    [&](int kk, int j) { return T(2) * sQb[kk * LDD + j]; }, [&](int i, int j) { return vr[i] * vq[j]; },
-                                    [&](int i, int j, T x) { emit(oF, b, t, i * d + j, x); });
-        wave_matmul_f64<2 * NP>(n, d, d, [&](int i, int kk) { return sF[i * LDD + kk]; }, [&](int kk, int j) { return sQb[kk * LDD + j]; },
-                                zero, [&](int i, int j, T x) { sT[i * LDD + j] = x; });
-        if (PASS == kPassC && of.p)
-            wave_matvec<T>(n, n, [&](int i, int j) { return sP[i * LDN + j]; }, [&](int j) { return vrb[j]; },
-                           [&](int i, T s) { emit(of, b, t, i, s); });
-        lds_sync();
-        // Vbar <- sym(T F' + rbar f') (through PF's tile), vbar <- rbar
-        wave_matmul_f64<2 * NP>(n, n, d, [&](int i, int kk) { return sT[i * LDD + kk]; }, [&](int kk, int j) { return sF[j * LDD + kk]; },
-                                [&](int i, int j) { return vrb[i] * vf[j]; }, [&](int i, int j, T x) { sPF[i * LDD + j] = x; });
-        lds_sync();
-        wave_for_2d(n, n, [&](int i, int j, int) { sVb[i * LDN + j] = T(0.5) * (sPF[i * LDD + j] + sPF[j * LDD + i]); });
-        for (int i = lane; i < n; i += kWave) vvb[i] = vrb[i];
-        lds_sync();
-        if (PASS == kPassC) {                                             // dC = Qbar, dc = qbar
-            if (oC.p) wave_for_2d(d, d, [&](int i, int j, int idx) { emit(oC, b, t, idx, sQb[i * LDD + j]); });
-            if (oc.p)
-                for (int i = lane; i < d; i += kWave) emit(oc, b, t, i, vq[i]);
-            lds_sync();
-        }
-        if (PASS == kPassA) {                                             // Psi <- A_cl Psi, A_cl = F_x + F_u K (through T's and PF's tiles)
-            wave_matmul_f64<NP>(n, n, m, [&](int i, int kk) { return sF[i * LDD + n + kk]; }, [&](int kk, int j) { return sK[kk * LDN + j]; },
-                                [&](int i, int j) { return sF[i * LDD + j]; }, [&](int i, int j, T x) { sT[i * LDD + j] = x; });
-            lds_sync();
-            wave_matmul_f64<NP>(n, n, n, [&](int i, int kk) { return sT[i * LDD + kk]; }, [&](int kk, int j) { return sPsi[kk * LDN + j]; },
-                                zero, [&](int i, int j, T x) { sPF[i * LDD + j] = x; });
-            lds_sync();
-            wave_for_2d(n, n, [&](int i, int j, int) { sPsi[i * LDN + j] = sPF[i * LDD + j]; });
-            lds_sync();
-        }
-    }
-
-    if (!status) {                     // the outgoing adjoint
-        if (PASS == kPassA) store_matrix(a.Psi + w * n * n, sPsi, LDN, n, n);
-        else store_matrix(a.Ws + w * n * n, sVb, LDN, n, n);
-        if (PASS != kPassB)
-            for (int i = lane; i < n; i += kWave) a.sv[w * n + i] = vvb[i];
-    }
-    if (lane == 0) *word = status;
-}
 
 // OR over the lanes of 8-bit status words
 __device__ __forceinline__ int wave_or8(int mine)
@@ -462,7 +297,7 @@ __global__ __launch_bounds__(kWave) void tvp_vjp_f64_finish_kernel(PvArgs a)
     if (!status) return;
     const int sizes[kOuts] = {n * d, n, d * d, d};
     for (int q = 0; q < kOuts; ++q) {
-        const PvOut &o = a.o[q];
+        const BvOut &o = a.o[q];
         if (!o.p) continue;
         const int slots = o.st ? N : 1;
         for (int t = 0; t < slots; ++t) fill_nan(o.p + (size_t)b * o.sb + (size_t)t * o.st, sizes[q]);
@@ -516,8 +351,8 @@ Layout layout(int B, int n, int count, size_t sum_doubles)
 template <int NP, int PASS>
 int sweep_for(const PvArgs &a, hipStream_t stream)
 {
-    return launch_with_lds(tvp_vjp_f64_sweep_kernel<NP, PASS>, (unsigned)((size_t)a.B * a.segments), kWave,
-                           PvLayout<NP>::total(PASS) * sizeof(double), stream, a);
+    return launch_with_lds(tvb_vjp_f64_kernel<NP, Periodic<PASS>>, (unsigned)((size_t)a.B * a.segments), kWave,
+                           BvLayout<NP>::total(PASS) * sizeof(double), stream, a);
 }
 
 template <int PASS>
@@ -580,14 +415,11 @@ int tfmpc_tvlqr_periodic_vjp_f64(int B, int n, int m, int N,
     const long st[kOuts] = {sdF_t, sdf_t, sdC_t, sdc_t};
     // a batch stride of 0 sums over the batch (over a batch of one the sum is the instance's own gradient, written in
     // place); a time stride of 0 sums over time in the sweep, in time order: the period is then ONE segment
-    unsigned summed = 0;
     int slots[kOuts];
+    const unsigned summed = batch_sum_select(B, kOuts, outs, sb, st, N, slots);
     bool time_shared = false;
-    for (int q = 0; q < kOuts; ++q) {
-        slots[q] = st[q] ? N : 1;
-        if (outs[q] && sb[q] == 0 && B > 1) summed |= 1u << q;
+    for (int q = 0; q < kOuts; ++q)
         if (outs[q] && st[q] == 0 && N > 1) time_shared = true;
-    }
     const SegmentTable tab = segment_table(N, time_shared ? 1 : segments);
     if ((size_t)B * tab.count > (size_t)INT32_MAX) return TFMPC_ERR_UNSUPPORTED;
     const BatchSumPlan plan = sum_plan(B, n, m, slots, summed);
@@ -604,11 +436,7 @@ int tfmpc_tvlqr_periodic_vjp_f64(int B, int n, int m, int N,
     a.K = K; a.k = k; a.V = V; a.v = v; a.fwd_status = fwd_status;
     a.gK = gK; a.gk = gk; a.gV = gV; a.gv = gv;
     double *const sums = w + L.sum;
-    for (int q = 0; q < kOuts; ++q) {
-        const long size = plan.size[q];
-        if (summed >> q & 1u) a.o[q] = {sums + plan.rec_off[q], (long)slots[q] * size, st[q] ? size : 0};
-        else a.o[q] = {outs[q], sb[q], st[q]};
-    }
+    batch_sum_route(plan, sums, outs, sb, st, [&](int q, double *p, long b, long t) { a.o[q] = {p, b, t}; });
     a.Psi = w + L.Psi; a.Ws = w + L.Ws; a.Xs = w + L.Xs; a.sv = w + L.sv; a.ys = w + L.ys; a.Phi = w + L.Phi;
     const size_t waves = (size_t)B * tab.count;
     int32_t *words = reinterpret_cast<int32_t *>(w + L.st);

@@ -1,11 +1,12 @@
 """Do two source trees compile to the same kernels?  The check behind "the parent's bits" in a kernel commit, without a GPU.
 
-    python tools/kernel_text_diff.py TREE_A TREE_B file.hip [file.hip:MACRO=VALUE ...]
+    python tools/kernel_text_diff.py [--pair OLD=NEW ...] TREE_A TREE_B file.hip [file.hip:MACRO=VALUE ...]
 
 Each file (a path inside the tree, or a bare name under tf-mpc_amd/csrc) is compiled in both trees to device assembly with
 check_ring_waits.FLAGS --cuda-device-only -S; `file.hip:MACRO=VALUE` adds -DMACRO=VALUE (ilqr_adjoint_mfma.hip:TFMPC_AM_PART=3).
 Kernels are paired by demangled name without the parameter list, so a renamed argument type still pairs (without llvm-cxxfilt or
-c++filt: by mangled name, and such a kernel is reported as unpaired).  Per kernel it compares
+c++filt: by mangled name, and such a kernel is reported as unpaired).  A kernel that was renamed on purpose is paired by hand:
+--pair OLD=NEW (repeatable; each side a substring of one demangled name, OLD in tree A, NEW in tree B).  Per kernel it compares
   * the instruction text between the kernel's label and its .amdhsa_kernel line: comments and directives stripped, block labels
     kept, the function index in .LBB<i>_<k> and the names of kernels and of the __hip_cuid_* symbol normalised;
   * .amdhsa_next_free_vgpr, .amdhsa_next_free_sgpr and .amdhsa_private_segment_fixed_size;
@@ -76,9 +77,13 @@ def kernels(text):
     return out
 
 
-def compare(a, b):
+def compare(a, b, pairs=()):
     """(kernels compared, list of findings) for the two assembly texts of one file"""
     ka, kb = kernels(a), kernels(b)
+    for old, new in pairs:                                 # a renamed kernel takes its old key, where both sides name exactly one
+        src, dst = [k for k in ka if old in k], [k for k in kb if new in k]
+        if len(src) == len(dst) == 1:
+            kb[src[0]] = kb.pop(dst[0])
     bad = 0
     for key in list(ka) + [k for k in kb if k not in ka]:
         if key not in ka or key not in kb:
@@ -99,15 +104,20 @@ def compare(a, b):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) < 4:
+    argv, pairs = sys.argv[1:], []
+    while "--pair" in argv[:-1]:
+        i = argv.index("--pair")
+        pairs.append(tuple(argv[i + 1].split("=", 1)))
+        del argv[i:i + 2]
+    if len(argv) < 3 or any(len(p) != 2 for p in pairs):
         sys.exit(__doc__)
-    tree_a, tree_b, specs = sys.argv[1], sys.argv[2], sys.argv[3:]
+    tree_a, tree_b, specs = argv[0], argv[1], argv[2:]
     total = bad = 0
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         jobs = [(spec, pool.submit(assembly, tree_a, spec, tmp), pool.submit(assembly, tree_b, spec, tmp)) for spec in specs]
         for spec, fa, fb in jobs:
             print(spec)
-            n, b = compare(fa.result(), fb.result())
+            n, b = compare(fa.result(), fb.result(), pairs)
             total += n
             bad += b
     print(f"{total} kernels in {len(specs)} translation units: {total - bad} identical, {bad} different or unpaired")
